@@ -6,6 +6,13 @@ Contract (see the task's bench section): ``python bench.py --gpus N --steps K
 --warmup W``; for N>1 it is launched under torch.distributed.run, one rank per
 GPU (RCCL).  Rank 0 prints ONE JSON line.
 
+A plain run does only what the headline figure needs: it builds the batch, runs W warm-up
+and K timed steps, writes the last timed step's results if ``--dump-outputs DIR`` is given
+(mean, std, score and match of every segment as ``DIR/<name>.npy``; the batch is seeded, so
+two runs with the same arguments score identical inputs) and prints the line (``value``,
+``ms_per_step`` = wall milliseconds per timed step, ``roofline`` from the timed steps' own
+kernel times).  ``--full`` adds every other leg described under "Extra fields" below.
+
 Workload (BASELINE.json configs[1], "1024 concurrent synthetic 16 kHz streams,
 MFCC+cosine match, 1xMI355X"): per GPU, 1024 streams x 64 gated segments =
 65536 ragged segments with L ~ U{6400..33600} samples, resident
@@ -21,7 +28,8 @@ compaction, an all_gather of the counts, point-to-point records.  Streams shard
 across ranks (weak scaling).
 
 Extra fields: ``roofline`` (dominant kernel k_score_f32, 640 algorithmic bytes
-per MFCC frame, HIP-event timed), ``cpu_baseline`` (oracle/mfcc_ref.py, the
+per MFCC frame, HIP-event timed); with ``--full`` also ``fixed_length`` / ``short_length``
+(the scorer on segments of one length), ``pcie_inclusive``, ``cpu_baseline`` (oracle/mfcc_ref.py, the
 librosa-0.11 restatement, on rank 0 at N=1 only, time-bounded sample),
 ``streaming`` (configs[2]: 8192 streams through the full level-1 + level-2
 engine, one tick per push), ``streaming_f32_max`` (as many resident streams as HBM holds
@@ -65,6 +73,13 @@ def parse():
     ap.add_argument("--streams", type=int, default=1024, help="streams per GPU (config 2)")
     ap.add_argument("--segments-per-stream", type=int, default=64)
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (mean, std, score, "
+                         "match of every segment) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline measurement also run every other leg (fixed-length and short "
+                         "segments, the PCIe-inclusive pass, the CPU baselines, the streaming legs with level 3 "
+                         "and host ingest); the options below select among those legs and need --full")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-streaming", action="store_true")
@@ -91,7 +106,10 @@ def parse():
     ap.add_argument("--host-streams-f32", type=int, default=131072)
     ap.add_argument("--host-streams-i16", type=int, default=1048576)
     ap.add_argument("--host-ticks", type=int, default=200, help="timed ticks of the host-ingest legs")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def load_word() -> np.ndarray:
@@ -143,6 +161,32 @@ def make_segments(torch, dev, n_seg, seed, word, fixed_len=0):
     frames = int((1 + lengths.astype(np.int64) // HOP).sum())
     return (pcm, torch.from_numpy(offsets).to(dev), torch.from_numpy(lengths).to(dev), frames,
             lengths, offsets)
+
+
+DUMP_BYTES_MAX = 64 * 10**6    # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir, seed, rank, world, arrays):
+    """Write the scorer's per-segment results (device tensors, first axis = segment) as
+    <out_dir>/<name>.npy (<name>_rank<r>.npy for N > 1): float32 stays float32, everything else
+    becomes float64 (match: 0.0 / 1.0).  A batch whose results exceed DUMP_BYTES_MAX is written
+    as a fixed sample of its segments, drawn from `seed`, with the sampled segments' ids in
+    segment_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a if a.dtype == np.float32 else a.astype(np.float64)
+    n = len(next(iter(host.values())))
+    row = sum(a.itemsize * int(np.prod(a.shape[1:], dtype=np.int64)) for a in host.values()) + 8
+    keep = DUMP_BYTES_MAX // (row * max(1, world)) - 16      # the .npy headers fit in the slack
+    if n > keep:
+        idx = np.sort(np.random.Generator(np.random.PCG64(seed)).choice(n, keep, replace=False))
+        host = {name: np.ascontiguousarray(a[idx]) for name, a in host.items()}
+        host["segment_index"] = idx.astype(np.float64)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), a)
 
 
 # --------------------------------------------------------------------------- CPU baseline
@@ -866,15 +910,19 @@ def main():
     value = float(frames_all.item()) * args.steps / t_max
     n_match = int(match.sum().item())
     n_nan = int(torch.isnan(score).sum().item())
+    if args.dump_outputs:   # the last timed step's results, before any other leg runs
+        dump_outputs(args.dump_outputs, args.seed, rank, world,
+                     {"mean": mean, "std": std, "score": score, "match": match})
 
+    full = args.full
     fixed = fixed_length_bench(torch, dev, ewa, eng, word, n_seg, args.seed + 1000 * rank, sh) \
-        if args.fixed_len > 0 and world == 1 else None
+        if full and args.fixed_len > 0 and world == 1 else None
     # the reference's shortest gated segment (0.4 s: speech_duration_min 0.3 s + padding), where
     # the per-segment fixed cost weighs most
     short = fixed_length_bench(torch, dev, ewa, eng, word, n_seg, args.seed + 1000 * rank, sh,
-                               fixed_len=args.short_len) if args.short_len > 0 and world == 1 else None
+                               fixed_len=args.short_len) if full and args.short_len > 0 and world == 1 else None
     pcie = pcie_inclusive_bench(torch, eng, pcm, lengths, offsets, frames) \
-        if args.pcie and world == 1 else None
+        if full and args.pcie and world == 1 else None
     kernel_s = (k_ms / max(1, k_n)) / 1e3
     achieved = frames * BYTES_PER_FRAME / kernel_s / 1e9
     traffic, traffic_src, compute = None, None, None
@@ -901,6 +949,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": full,
         "ms_per_step": t_max / args.steps * 1e3,
         "higher_is_better": True,
         "scaling": "weak",
@@ -949,14 +998,15 @@ def main():
                               "gather": "positives held on the device over the timed loop, one counts all_gather + "
                                         "point-to-point records to rank 0 after its last step (inside the timing)"}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    streaming = full and not args.no_streaming
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sample = min(n_seg, max(16, host_cores()[0]) * 400)
         host = pcm[: int(offsets[sample - 1] + lengths[sample - 1])].cpu().numpy()
         out["cpu_baseline"] = cpu_baseline(host, lengths[:sample], offsets[:sample], args.cpu_seconds)
-        if not args.no_streaming:
+        if streaming:
             out["cpu_baseline"]["streaming"] = cpu_stream_baseline(min(args.cpu_seconds, 10.0),
                                                                    out["cpu_baseline"]["cores"])
-    if not args.no_streaming:
+    if streaming:
         del pcm
         torch.cuda.empty_cache()
         st = streaming_bench(torch, dev, ewa, args.stream_count, args.stream_ticks, args.seed + rank, word,

@@ -6,7 +6,7 @@ R=${1:-2}; BIG=${2:-0}; MAX=${3:-0}
 for r in $(seq 1 $R); do
   for f in ${VDIR:-variants}/*.so; do
     echo -n "$(basename $f) "
-    EWK_LIB=$PWD/$f timeout -k 10 300 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --fixed-len 0 --confirm-batch 0 \
+    EWK_LIB=$PWD/$f timeout -k 10 300 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --fixed-len 0 --confirm-batch 0 \
         --big-streams $BIG --max-streams $MAX 2>/dev/null | \
       python -c "
 import json,sys; d=json.loads(sys.stdin.read()); s=d['streaming']

@@ -4,22 +4,22 @@
 #   bench      : default bench line
 #   stream     : the 8,192-stream tick (mb_stream.py) and the tick histogram
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out
+OUT="${EWK_OUT:-$PWD/out}"; mkdir -p "$OUT"   # logs and profiler output
 MODE=${1:-test}
 TAG=${TAG:-r04}
 ok_or_testfail() { local rc=$1; [ $rc -eq 0 ] || [ $rc -eq 1 ]; }
 if [ "$MODE" = test ]; then
   K=${2:+-k $2}
-  timeout -k 10 1100 python -u -m pytest tests -v -m gpu -x -p no:cacheprovider --timeout 300 --timeout-method thread $K > gpurun_out/${TAG}_pytest_gpu.log 2>&1
-  rc=$?; echo "pytest rc=$rc"; tail -15 gpurun_out/${TAG}_pytest_gpu.log
+  timeout -k 10 1100 python -u -m pytest tests -v -m gpu -x -p no:cacheprovider --timeout 300 --timeout-method thread $K > $OUT/${TAG}_pytest_gpu.log 2>&1
+  rc=$?; echo "pytest rc=$rc"; tail -15 $OUT/${TAG}_pytest_gpu.log
   ok_or_testfail $rc || exit $rc
-  timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${TAG}_smoke.log 2>&1
-  rc=$?; echo "smoke rc=$rc"; tail -3 gpurun_out/${TAG}_smoke.log
+  timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/${TAG}_smoke.log 2>&1
+  rc=$?; echo "smoke rc=$rc"; tail -3 $OUT/${TAG}_smoke.log
   exit $rc
 fi
 if [ "$MODE" = bench ]; then
-  timeout -k 10 900 python bench.py --steps 20 --warmup 10 > gpurun_out/${TAG}_bench.log 2>&1
-  rc=$?; echo "bench rc=$rc"; tail -c 1500 gpurun_out/${TAG}_bench.log
+  timeout -k 10 900 python bench.py --full --steps 20 --warmup 10 > $OUT/${TAG}_bench.log 2>&1
+  rc=$?; echo "bench rc=$rc"; tail -c 1500 $OUT/${TAG}_bench.log
   exit $rc
 fi
 if [ "$MODE" = ab ]; then   # interleaved A/B of variants/*.so: ragged, L = 16000, L = 6400
@@ -32,16 +32,16 @@ if [ "$MODE" = ab ]; then   # interleaved A/B of variants/*.so: ragged, L = 1600
         if [ $rc -ne 0 ]; then echo "variant $f rc=$rc"; exit $rc; fi
       done
     done
-  done | tee gpurun_out/${TAG}_ab.txt
+  done | tee $OUT/${TAG}_ab.txt
   exit ${PIPESTATUS[0]}
 fi
 if [ "$MODE" = probe ]; then
-  timeout -k 5 60 ./scripts/probes/buffer_lds_probe 2>&1 | tee gpurun_out/${TAG}_buffer_lds_probe.txt
+  timeout -k 5 60 ./scripts/probes/buffer_lds_probe 2>&1 | tee $OUT/${TAG}_buffer_lds_probe.txt
   exit ${PIPESTATUS[0]}
 fi
 if [ "$MODE" = varcheck ]; then   # parity subset on a variant: EWK_LIB=variants/<v>.so
   V=${2:-variants/b_prefetch_dma.so}
-  EWK_LIB=$PWD/$V timeout -k 10 900 python -u -m pytest tests/test_gpu_scorer.py tests/test_gpu_many_streams.py tests/test_gpu_vanishing_mean.py -v -m gpu -x -p no:cacheprovider --timeout 300 --timeout-method thread > gpurun_out/${TAG}_varcheck.log 2>&1
-  rc=$?; echo "varcheck $V rc=$rc"; tail -5 gpurun_out/${TAG}_varcheck.log
+  EWK_LIB=$PWD/$V timeout -k 10 900 python -u -m pytest tests/test_gpu_scorer.py tests/test_gpu_many_streams.py tests/test_gpu_vanishing_mean.py -v -m gpu -x -p no:cacheprovider --timeout 300 --timeout-method thread > $OUT/${TAG}_varcheck.log 2>&1
+  rc=$?; echo "varcheck $V rc=$rc"; tail -5 $OUT/${TAG}_varcheck.log
   exit $rc
 fi
