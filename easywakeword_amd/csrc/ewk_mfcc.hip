@@ -33,9 +33,12 @@
 //             splits (Dh Xh + Dh Xl + Dl Xh, f32 accumulation), rows 20..31 zero.
 //   top_db  : power_to_db clamps at (segment max - 80 dB), a segment-global coupling.
 //             Pass 1 clamps each tile speculatively at the running max - 80 dB (exact
-//             once the max is known) and records the stored tile minimum; if the segment
-//             min is below the final max - 80 dB, pass 2 recomputes only the tiles whose
-//             stored minimum is below it and swaps their contribution in the statistics
+//             once the max is known).  When the clamp rises later, a stored tile's clamped
+//             entries only have to move up with it: the DCT is linear, so the tile's mask
+//             DCT m = D . [entry clamped] shifts its columns by (rise) m inside the shifted
+//             sums (ewk_topdb_shift.h), no recompute.  Only a tile holding an unclamped
+//             value below the final max - 80 dB (its recorded minimum above the clamp) is
+//             recomputed in pass 2 and its contribution swapped in the statistics
 //             (nothing is written to global memory but the results).
 //   stats   : population mean/std over frames from fp64 shifted sums
 //             (d = c - c[frame 0]) -- exact 0 std for identical frames.
@@ -47,6 +50,7 @@
 
 #include "ewk_internal.h"
 #include "ewk_db64.h"   // (the fp64 re-score's 10 log10, ewk_rescore.h)
+#include "ewk_topdb_shift.h"
 
 // s_setprio 1 over the frame-pass LDS phases (window, transposes, mel): -0.4 %
 #define EWK_SETPRIO(v) __builtin_amdgcn_s_setprio(v)
@@ -71,7 +75,7 @@
 #define EWK_PASS_ARG(x)
 #endif
 #ifdef EWK_TIMING
-constexpr int kDbgN = 20;
+constexpr int kDbgN = 24;   // [20] masked tiles, [21] cycles of their DCT + mask DCT + sums, [22] [23] cycles and count of the plain tile DCTs
 #endif
 
 namespace ewk {
@@ -143,22 +147,28 @@ constexpr int L_DCT = L_BLO + NMEL * 4;
 // products hi*hi + hi*lo + lo*hi carry ~22 bits).  The tile's k order groups each lane's
 // eight bands: k-chunk c (k = 8c .. 8c+7) holds bands c + 16 jj, jj = 0..7, so the
 // operand of k-step q for lane l is chunk 4q + (l >> 4).  Row tile 0 (coefficients 0..15):
-// [q][hi/lo][lane] 16-B chunks; row tile 1 (coefficients 16..19): [q][hi/lo][l >> 4][l & 3]
-// for the lanes with (l & 15) < 4, every other lane reads the block's zero chunk.
+// [q][hi/lo][lane] 16-B chunks; row tile 1 (coefficient 16 + n in row 4n, so that each lane
+// group of the output holds one of them): [q][hi/lo][l >> 4][n] for the lanes with
+// (l & 15) = 4n, every other lane reads the block's zero chunk.
 constexpr float kDctScale = 1024.0f;
 constexpr float kTopDbUnits = 80.0f;   // top_db, in the tile's dB units
 constexpr int DCT_RT1 = 4 * 2 * 64 * 16;                  // row tile 1: [q][hi/lo] blocks of 17 chunks
-constexpr int DCT_RT1_STRIDE = 17 * 16;                   // 16 data chunks [l >> 4][l & 3] + a zero chunk
+constexpr int DCT_RT1_STRIDE = 17 * 16;                   // 16 data chunks [l >> 4][(l & 15) >> 2] + a zero chunk
+// coefficient slots per lane: rows 4h .. 4h + 3 of row tile 0, and row 4h of row tile 1, which
+// holds coefficient 16 + h (rows 4h + 1 .. 4h + 3 of that tile are zero and are not kept)
+constexpr int kSlots = 5;
 constexpr int DCT_BYTES = DCT_RT1 + 8 * DCT_RT1_STRIDE;
 constexpr int L_SHARED_END = ((L_DCT + DCT_BYTES) + 15) & ~15;
 constexpr int W_TILE = 0;                                 // 16 frame rows x 512 B of f16 hi/lo chunks (tile_chunk)
 // per-tile record of the speculative top_db clamp (segment_stats): stored log-mel minima per
-// pass, the clamps and the processing order ((passes per tile + 2) x kSpecTiles ints)
+// pass (above the clamp, for a tile with clamped entries), the clamps and the processing order
+// ((passes per tile + 2) x kSpecTiles ints)
 constexpr int kSpecTiles = 48;   // tiles of frames 0..767 (7.7 s) are recorded and scout-ordered
 constexpr int W_SPEC = W_TILE + 16 * NMEL * 4;
 constexpr int kSpecRun = (16 / kFPP) * kSpecTiles;      // spec[kSpecRun + tile]: the tile's clamp
 constexpr int kSpecOrder = kSpecRun + kSpecTiles;        // spec[kSpecOrder + k]: k-th tile processed
 constexpr int W_BYTES = W_SPEC + (kSpecOrder + kSpecTiles) * 4;
+static_assert(W_BYTES % 16 == 0 && kSpecTiles <= 64, "per-wave LDS carve; one bit per recorded tile");
 constexpr int L_WG = L_SHARED_END + WAVES * W_BYTES;    // ring mode: segment index + per-wave log-mel max/min
 constexpr int LDS_BYTES = L_WG + 16 + 8 * WAVES;
 constexpr int kRescoreFrames = 16;
@@ -810,8 +820,8 @@ __device__ __forceinline__ void frame_pass(const SegSrc<RING>& v, int t0, int T,
 // DCT of one 16-frame log-mel tile on the matrix cores: C[32 x 16] = D[32 x 128] X[128 x 16]
 // with v_mfma_f32_16x16x32_f16 on the f16 hi/lo splits, three products per k-step
 // (Dh Xh + Dh Xl + Dl Xh, f32 accumulation; the dropped Dl Xl is ~2^-22 relative).
-// Lane l gets C[row = 4h + r][frame col] of both row tiles (h = l>>4, col = l&15) in
-// c[0..3], c[4..7] -- the layout of the f32 16x16x4 MFMA.  The operands of k-step q
+// Lane l gets C[row = 4h + r][frame col] of row tile 0 (h = l>>4, col = l&15) in c[0..3] and
+// row 4h of row tile 1 (coefficient 16 + h) in c[4] -- the layout of the f32 16x16x4 MFMA.  The operands of k-step q
 // (6 ds_read_b128) are requested one step ahead of its 6 MFMAs.
 #define EWK_DCT_RD(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(off) : "memory")
 #define EWK_DCT_LOAD(p, q)                                                   \
@@ -835,10 +845,72 @@ __device__ __forceinline__ void frame_pass(const SegSrc<RING>& v, int t0, int T,
         EWK_MF(A0h[p], Bh[p], acc0); EWK_MF(A1h[p], Bh[p], acc1);                              \
         EWK_MF(A0h[p], Bl[p], acc0); EWK_MF(A1h[p], Bl[p], acc1);                              \
         EWK_MF(A0l[p], Bh[p], acc0); EWK_MF(A1l[p], Bh[p], acc1);                              \
+        if (MASK) {                                                                            \
+            const floatx4 mk = clamp_mask(Bh[p], Bl[p], cp, mnab);                             \
+            EWK_MF(A0h[p], mk, am0); EWK_MF(A1h[p], mk, am1);                                  \
+            EWK_MF(A0l[p], mk, am0); EWK_MF(A1l[p], mk, am1);                                  \
+        }                                                                                      \
     } while (0)
-__device__ __forceinline__ void tile_dct(const float* tile, const float* s_dct, int lane, float (&c)[8]) {
+
+// The split pair of a tile's clamp, as its clamped entries hold it (both halves of each word),
+// and its value float(hi) + float(lo).
+// float(hi) + float(lo) of the low / high entry of a pair word in one v_fma_mix_f32 (both
+// conversions exact, one rounding: the value clamp_store rebuilds)
+__device__ __forceinline__ float pair_sum_lo(uint32_t h, uint32_t l) {
+    float r;
+    asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel_hi:[1,0,1]" : "=v"(r) : "v"(h), "v"(l));
+    return r;
+}
+__device__ __forceinline__ float pair_sum_hi(uint32_t h, uint32_t l) {
+    float r;
+    asm("v_fma_mix_f32 %0, %1, 1.0, %2 op_sel:[1,0,1] op_sel_hi:[1,0,1]" : "=v"(r) : "v"(h), "v"(l));
+    return r;
+}
+struct ClampPair {
+    uint32_t h2, l2;
+    float eff;
+};
+__device__ __forceinline__ ClampPair clamp_pair(float clampv) {
+    ClampPair cp;
+    split2(clampv, clampv, cp.h2, cp.l2);
+    cp.eff = pair_sum_lo(cp.h2, cp.l2);
+    return cp;
+}
+// One B operand (eight entries of a frame row, hi and lo chunks): the f16 0/1 mask of the
+// entries that hold the clamp's pair, and the minimum of all the others into mn (an entry with
+// another pair counts as unclamped whatever its value: the record can only flag too often).
+// Per pair word: t has a zero half where the entry is the clamp's pair; min(t, 1) - 1 turns
+// that half into 0xFFFF and any other into 0 (packed u16); the mask word is 0x3C00 (f16 1.0)
+// there, and the hi word gets +inf (0x7C00) there so that the clamped entries drop out of the
+// minimum without a compare (inf + lo = inf).
+__device__ __forceinline__ floatx4 clamp_mask(floatx4 bh, floatx4 bl, const ClampPair& cp, float& mn) {
+    const uint4 h = __builtin_bit_cast(uint4, bh), l = __builtin_bit_cast(uint4, bl);
+    const uint32_t hw[4] = {h.x, h.y, h.z, h.w}, lw[4] = {l.x, l.y, l.z, l.w};
+    const uint32_t ones = 0x00010001u;
+    uint32_t mw[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t t = (hw[k] ^ cp.h2) | (lw[k] ^ cp.l2);
+        uint32_t u, zm;
+        asm("v_pk_min_u16 %0, %1, %2" : "=v"(u) : "v"(t), "s"(ones));
+        asm("v_pk_sub_u16 %0, %1, %2" : "=v"(zm) : "v"(u), "s"(ones));
+        mw[k] = zm & 0x3C003C00u;
+        const uint32_t hm = (zm & 0x7C007C00u) | (hw[k] & ~zm);
+        // (v_min3_f32 written out: fminf on the asm results costs a canonicalising v_max each)
+        asm("v_min3_f32 %0, %0, %1, %2" : "+v"(mn) : "v"(pair_sum_lo(hm, lw[k])), "v"(pair_sum_hi(hm, lw[k])));
+    }
+    return __builtin_bit_cast(floatx4, make_uint4(mw[0], mw[1], mw[2], mw[3]));
+}
+
+// MASK: the tile holds entries clamped at `cp`; also returns their mask DCT m = (Dh + Dl) . mask
+// (the mask is exact in f16: two products per k-step and row tile) and the lane's minimum of
+// the unclamped entries of its frame row chunks (mnab, folded into the caller's value).
+template <bool MASK>
+__device__ __forceinline__ void tile_dct_m(const float* tile, const float* s_dct, int lane, float (&c)[kSlots],
+                                           float (&m)[kSlots], float& mnab, const ClampPair& cp) {
     const int col = lane & 15, g4 = lane >> 4;
     floatx4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+    floatx4 am0 = {0.f, 0.f, 0.f, 0.f}, am1 = {0.f, 0.f, 0.f, 0.f};
     // B of k-step q: chunk 4q + g4 of frame row col, at slot (4q + g4) ^ col =
     // 4 (q ^ (col >> 2)) + (g4 ^ (col & 3))
     const uint32_t tb = (uint32_t)(uintptr_t)tile + 512 * col + 16 * (g4 ^ (col & 3));
@@ -847,7 +919,7 @@ __device__ __forceinline__ void tile_dct(const float* tile, const float* s_dct, 
     for (int q = 0; q < 4; ++q) bq[q] = tb + 64 * (q ^ (col >> 2));
     const uint32_t db = (uint32_t)(uintptr_t)s_dct;
     const uint32_t a0 = db + 16 * lane;
-    const uint32_t a1 = db + DCT_RT1 + 16 * (col < 4 ? 4 * g4 + col : 16);
+    const uint32_t a1 = db + DCT_RT1 + 16 * ((col & 3) == 0 ? 4 * g4 + (col >> 2) : 16);
     floatx4 Bh[2], Bl[2], A0h[2], A0l[2], A1h[2], A1l[2];
     EWK_DCT_LOAD(0, 0);
     EWK_DCT_LOAD(1, 1);
@@ -863,7 +935,17 @@ __device__ __forceinline__ void tile_dct(const float* tile, const float* s_dct, 
     EWK_DCT_MFMA(1);
     lds_order();
 #pragma unroll
-    for (int i = 0; i < 4; ++i) { c[i] = acc0[i] * (1.0f / kDctScale); c[4 + i] = acc1[i] * (1.0f / kDctScale); }
+    for (int i = 0; i < 4; ++i) c[i] = acc0[i] * (1.0f / kDctScale);
+    c[4] = acc1[0] * (1.0f / kDctScale);
+    if (MASK) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) m[i] = am0[i] * (1.0f / kDctScale);
+        m[4] = am1[0] * (1.0f / kDctScale);
+    }
+}
+__device__ __forceinline__ void tile_dct(const float* tile, const float* s_dct, int lane, float (&c)[kSlots]) {
+    float m[kSlots], mnab = 0.0f;
+    tile_dct_m<false>(tile, s_dct, lane, c, m, mnab, ClampPair{0u, 0u, 0.0f});
 }
 #undef EWK_DCT_RD
 #undef EWK_DCT_LOAD
@@ -872,11 +954,11 @@ __device__ __forceinline__ void tile_dct(const float* tile, const float* s_dct, 
 #undef EWK_MF
 
 // fp64 shifted sums of the frame columns that exist (d = c - cref).
-__device__ __forceinline__ void stats_add(const float (&c)[8], const float (&cref)[8], bool ok, double (&s1)[8],
-                                          double (&s2)[8]) {
+__device__ __forceinline__ void stats_add(const float (&c)[kSlots], const float (&cref)[kSlots], bool ok, double (&s1)[kSlots],
+                                          double (&s2)[kSlots]) {
     if (ok) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
+        for (int i = 0; i < kSlots; ++i) {
             const double d = (double)c[i] - (double)cref[i];
             s1[i] += d;
             s2[i] = fma(d, d, s2[i]);
@@ -885,15 +967,58 @@ __device__ __forceinline__ void stats_add(const float (&c)[8], const float (&cre
 }
 
 // Swap one tile's contribution: remove the unclamped columns `co`, add the clamped `cn`.
-__device__ __forceinline__ void stats_replace(const float (&cn)[8], const float (&co)[8], const float (&cref)[8],
-                                              bool ok, double (&s1)[8], double (&s2)[8]) {
+__device__ __forceinline__ void stats_replace(const float (&cn)[kSlots], const float (&co)[kSlots], const float (&cref)[kSlots],
+                                              bool ok, double (&s1)[kSlots], double (&s2)[kSlots]) {
     if (ok) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
+        for (int i = 0; i < kSlots; ++i) {
             const double dn = (double)cn[i] - (double)cref[i], dd = (double)co[i] - (double)cref[i];
             s1[i] += dn - dd;
             s2[i] += fma(dn, dn, -dd * dd);
         }
+    }
+}
+
+// ---- top_db shift sums (ewk_topdb_shift.h): A, B, C per lane and coefficient slot, in float32
+// next to s1 / s2 (the registers of the three row-tile-1 slots that hold no coefficient).
+// A masked tile's columns (c at the tile's clamp, m its mask DCT) join the sums.
+__device__ __forceinline__ void shift_tile_add(const float (&c)[kSlots], const float (&cref)[kSlots],
+                                               const float (&m)[kSlots], bool ok, float (&sA)[kSlots],
+                                               float (&sB)[kSlots], float (&sC)[kSlots]) {
+    if (ok) {
+#pragma unroll
+        for (int i = 0; i < kSlots; ++i) shift_add<float, float>(c[i] - cref[i], m[i], sA[i], sB[i], sC[i]);
+    }
+}
+// The clamp of every column in the sums rises by delta.
+__device__ __forceinline__ void shift_apply(double delta, const float (&sA)[kSlots], float (&sB)[kSlots],
+                                            const float (&sC)[kSlots], double (&s1)[kSlots], double (&s2)[kSlots]) {
+#pragma unroll
+    for (int i = 0; i < kSlots; ++i) shift_rise<float, float>(delta, sA[i], sB[i], sC[i], s1[i], s2[i]);
+}
+// Swap one masked tile's contribution: out go its stored columns as shifted to theta.
+__device__ __forceinline__ void stats_replace_shift(const float (&cn)[kSlots], const float (&co)[kSlots], const float (&m)[kSlots],
+                                                    double delta, const float (&cref)[kSlots], bool ok, double (&s1)[kSlots],
+                                                    double (&s2)[kSlots]) {
+    if (ok) {
+#pragma unroll
+        for (int i = 0; i < kSlots; ++i)
+            shift_replace((double)cn[i], (double)co[i], (double)m[i], delta, (double)cref[i], s1[i], s2[i]);
+    }
+}
+
+// Minima of a float over the lanes of each 8-frame pass of a tile (frame column & 8), no LDS.
+__device__ __forceinline__ void pass_mins(float x, float (&pm)[2]) {
+    x = fminf(x, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(x), __float_as_int(x), 0x111, 0xf, 0xf, false)));
+    x = fminf(x, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(x), __float_as_int(x), 0x112, 0xf, 0xf, false)));
+    x = fminf(x, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(x), __float_as_int(x), 0x114, 0xf, 0xf, false)));
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {   // lane 7 of a row: columns 0..7; lane 15: columns 8..15
+        const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 7 + 8 * p));
+        const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 23 + 8 * p));
+        const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 39 + 8 * p));
+        const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 55 + 8 * p));
+        pm[p] = fminf(fminf(r0, r1), fminf(r2, r3));
     }
 }
 
@@ -956,10 +1081,10 @@ __device__ __forceinline__ float wave_max(float x) { return -wave_min(-x); }
 // row), hand each coefficient's (S1, S2, cref) to lane k = coefficient through the
 // wave's scratch `pd` (20 x 3 doubles), and finish there: lane k < 20 returns its mean in
 // s1[0] and its population std in s2[0] (one fp64 division + sqrt per lane, not eight).
-__device__ __forceinline__ void finish_stats(int T, const float (&cref)[8], double (&s1)[8], double (&s2)[8],
+__device__ __forceinline__ void finish_stats(int T, const float (&cref)[kSlots], double (&s1)[kSlots], double (&s2)[kSlots],
                                              int lane, double* pd) {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
+    for (int i = 0; i < kSlots; ++i) {
         s1[i] = row_sum_d(s1[i]);
         s2[i] = row_sum_d(s2[i]);
     }
@@ -969,11 +1094,9 @@ __device__ __forceinline__ void finish_stats(int T, const float (&cref)[8], doub
         for (int r = 0; r < 4; ++r) {
             const int k = 4 * h + r;
             pd[3 * k] = s1[r]; pd[3 * k + 1] = s2[r]; pd[3 * k + 2] = (double)cref[r];
-            if (h == 0) {
-                const int k2 = 16 + r;
-                pd[3 * k2] = s1[4 + r]; pd[3 * k2 + 1] = s2[4 + r]; pd[3 * k2 + 2] = (double)cref[4 + r];
-            }
         }
+        const int k2 = 16 + h;   // slot 4 of row h: coefficient 16 + h
+        pd[3 * k2] = s1[4]; pd[3 * k2 + 1] = s2[4]; pd[3 * k2 + 2] = (double)cref[4];
     }
     lds_order();
     if (lane < NMFCC) {
@@ -1044,13 +1167,17 @@ __device__ __forceinline__ void tile_passes(const SegSrc<RING>& v, int tile_i, i
 template <int RING>
 __device__ __forceinline__ void fix_tile(const SegSrc<RING>& v, int tile_i, int T, float run, float theta,
                                          const unsigned char* smem, float* scr, float* tile, int lane,
-                                         const int (&lo)[8], const float (&cref)[8], double (&s1)[8],
-                                         double (&s2)[8], int mask = kAllPasses) {
+                                         const int (&lo)[8], const float (&cref)[kSlots], double (&s1)[kSlots],
+                                         double (&s2)[kSlots], int mask = kAllPasses, bool shifted = false) {
     const float* s_dct = reinterpret_cast<const float*>(smem + L_DCT);
     float d0 = 0.f, d1 = 0.f, d2 = 0.f;
     tile_passes(v, tile_i, T, smem, scr, tile, lane, lo, d0, d1, d2, run, mask);
-    float co[8], cn[8];
-    tile_dct(tile, s_dct, lane, co);
+    float co[kSlots], cn[kSlots], m[kSlots];
+    // shifted: the tile's clamped entries went into the shift sums (segment_stats) and the
+    // rises since have moved its stored columns to co + (theta - run) m
+    const ClampPair cp = clamp_pair(run), ct = clamp_pair(theta);
+    if (shifted) tile_dct_m<true>(tile, s_dct, lane, co, m, d0, cp);
+    else tile_dct(tile, s_dct, lane, co);
     {
         uint4 h[4], l[4];
         clamp_load(reinterpret_cast<const float4*>(tile), lane, h, l);
@@ -1059,7 +1186,9 @@ __device__ __forceinline__ void fix_tile(const SegSrc<RING>& v, int tile_i, int 
     lds_order();
     tile_dct(tile, s_dct, lane, cn);
     const int col = lane & 15;
-    stats_replace(cn, co, cref, tile_i * 16 + col < T && ((mask >> (col / kFPP)) & 1), s1, s2);
+    const bool ok = tile_i * 16 + col < T && ((mask >> (col / kFPP)) & 1);
+    if (shifted) stats_replace_shift(cn, co, m, (double)ct.eff - (double)cp.eff, cref, ok, s1, s2);
+    else stats_replace(cn, co, cref, ok, s1, s2);
 }
 
 // Scout of a segment's tiles (tile t: frames 16t .. 16t + 15): the energy of 4 x 64 of its
@@ -1177,18 +1306,21 @@ __device__ __forceinline__ void work_describe(const WorkCtx& c, WorkAhead& w) {
 }
 
 // Whole segment for one wave.  spec: this wave's per-tile record in LDS -- the stored
-// log-mel minimum of pass p of tile i in spec[kPassesPerTile * i + p], the tile's
+// log-mel minimum of pass p of tile i (of the values above the clamp, for a tile that holds
+// clamped entries) in spec[kPassesPerTile * i + p], the tile's
 // speculative clamp in spec[kSpecRun + i] (tiles past kSpecTiles are stored unclamped and
 // always recomputed when theta bites), then the processing order (spec[kSpecOrder + k]).
 //
 // The top_db clamp (max - 80 dB over the whole segment) is applied speculatively at the
 // running max, which each tile updates before its DCT; a tile that already holds the
 // segment max needs no fix, so the tiles are processed loudest first by a scout estimate
-// (bench batch: 16 % of the tiles recomputed in time order, ~5 % in scout order), and only
-// the passes of a tile that hold a value below the final threshold are recomputed.
+// (bench batch: 16 % of the tiles recomputed in time order, ~5 % in scout order).  When the
+// clamp rises, the clamped entries of the earlier tiles move up with it inside the sums
+// (ewk_topdb_shift.h); only the passes of a tile that hold an unclamped value below the final
+// threshold are recomputed (0.06 per bench segment).
 template <int RING>
 __device__ void segment_stats(const SegSrc<RING>& v, const unsigned char* smem, float* scr, float* tile,
-                              float* spec, int lane, const int (&lo)[8], double (&s1)[8], double (&s2)[8],
+                              float* spec, int lane, const int (&lo)[8], double (&s1)[kSlots], double (&s2)[kSlots],
                               float& theta_out, const WorkCtx& wc, WorkAhead& nx EWK_DBG_PARAM) {
     EWK_TS(tq0);
     const float* s_dct = reinterpret_cast<const float*>(smem + L_DCT);
@@ -1211,10 +1343,10 @@ __device__ void segment_stats(const SegSrc<RING>& v, const unsigned char* smem, 
     }
     EWK_TS(tq1);
     EWK_TADD(1, tq0, tq1);
-    float cref[8];
+    float cref[kSlots];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) { s1[i] = 0.0; s2[i] = 0.0; cref[i] = 0.0f; }
-    float vmax = -INFINITY, vmin = INFINITY, nanp = 0.0f;
+    for (int i = 0; i < kSlots; ++i) { s1[i] = 0.0; s2[i] = 0.0; cref[i] = 0.0f; }
+    float vmax = -INFINITY, nanp = 0.0f;
     int tile_i = ordered ? order[0] : 0;
     {   // stage the first pass synchronously
         float r[kStageLoads];
@@ -1225,6 +1357,16 @@ __device__ void segment_stats(const SegSrc<RING>& v, const unsigned char* smem, 
     EWK_TS(tq2);
     EWK_TADD(2, tq1, tq2);
     float run = -INFINITY;   // speculative clamp: running max - 80 dB
+    // top_db shift (ewk_topdb_shift.h): srun = the clamp at which the clamped entries of the
+    // recorded tiles so far sit in the sums, nshift = some tile has joined the shift sums,
+    // shifted = which tiles have, amin = the smallest record (what pass 2 has to look at)
+    static_assert(kPassesPerTile == 2, "pass_mins splits a tile in two passes");
+    float srun = -INFINITY, amin = INFINITY;
+    int nshift = 0;
+    float sA[kSlots], sB[kSlots], sC[kSlots];
+#pragma unroll
+    for (int i = 0; i < kSlots; ++i) { sA[i] = 0.0f; sB[i] = 0.0f; sC[i] = 0.0f; }
+    uint64_t shifted = 0;
     for (int k = 0; k < ntile; ++k) {
         EWK_TS(tk0);
         const int next_tile = k + 1 < ntile ? (ordered ? order[k + 1] : k + 1) : -1;
@@ -1262,23 +1404,53 @@ __device__ void segment_stats(const SegSrc<RING>& v, const unsigned char* smem, 
             lds_order();
         }
         run = fmaxf(run, run2);
-        float c[8];
-        tile_dct(tile, s_dct, lane, c);
+        // the clamp rose: the clamped entries of the tiles before this one move up with it
+        if (rec) {
+            if (nshift && run > srun) shift_apply((double)clamp_pair(run).eff - (double)clamp_pair(srun).eff, sA, sB, sC, s1, s2);
+            srun = run;
+        }
+        // a tile with clamped entries (only such a tile can be wrong once the max rises again):
+        // its mask DCT joins the shift sums and its record is the minimum above the clamp
+        const bool masked = rec && tmw < run;
+        const bool ok = tile_i * 16 + col < T;
+        float c[kSlots], m[kSlots], mnab = INFINITY;
+        EWK_TS(tm0);
+        if (masked) tile_dct_m<true>(tile, s_dct, lane, c, m, mnab, clamp_pair(run));
+        else tile_dct(tile, s_dct, lane, c);
+        EWK_TS(tm1);
         if (k == 0) {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) cref[i] = __shfl(c[i], lane & 48, 64);
+            for (int i = 0; i < kSlots; ++i) cref[i] = __shfl(c[i], lane & 48, 64);
         }
-        stats_add(c, cref, tile_i * 16 + col < T, s1, s2);
-        vmin = fminf(vmin, tmw);
+        stats_add(c, cref, ok, s1, s2);
+        float pm[kPassesPerTile] = {INFINITY, INFINITY};
+        EWK_TS(tm3);
+        if (masked) {
+            shift_tile_add(c, cref, m, ok, sA, sB, sC);
+            nshift = 1;
+            shifted |= 1ull << tile_i;
+            pass_mins(ok ? mnab : INFINITY, pm);
+            amin = fminf(amin, fminf(pm[0], pm[1]));
+#ifdef EWK_TIMING   // the mask phase: a masked tile's DCT with the mask DCT, its sums and minima
+            EWK_TS(tm2);
+            dbg[20] += 1;
+            dbg[21] += (tm1 - tm0) + (tm2 - tm3);
+#endif
+        } else {
+            amin = fminf(amin, fmaxf(tmw, run));
+        }
         if (lane == 0 && rec) {   // stored minima: the pass minima as clamped at the tile's run
 #pragma unroll
             for (int p = 0; p < kPassesPerTile; ++p)
-                spec[kPassesPerTile * tile_i + p] = fmaxf(spec[kPassesPerTile * tile_i + p], run);
+                spec[kPassesPerTile * tile_i + p] = masked ? pm[p] : fmaxf(spec[kPassesPerTile * tile_i + p], run);
             spec[kSpecRun + tile_i] = run;
         }
         tile_i = next_tile;
         EWK_TS(tk2);
         EWK_TADD(4, tk1, tk2);
+#ifdef EWK_TIMING
+        if (!masked) { dbg[22] += tm1 - tm0; dbg[23] += 1; }   // the plain DCT the mask phase is set against
+#endif
     }
     EWK_TS(tq3);
     if (wc.ahead) work_describe<RING>(wc, nx);
@@ -1286,15 +1458,17 @@ __device__ void segment_stats(const SegSrc<RING>& v, const unsigned char* smem, 
     vmax = wave_max(vmax);
     const float theta = vmax - kTopDbUnits;
     theta_out = theta;
-    if (vmin < theta) {
+    // the last rise, to the final threshold: every stored clamped entry now sits at theta
+    if (nshift && theta > srun) shift_apply((double)clamp_pair(theta).eff - (double)clamp_pair(srun).eff, sA, sB, sC, s1, s2);
+    if (amin < theta) {   // some tile holds an unclamped value below theta
         lds_order();
         for (int cur = 0; cur < ntile; ++cur) {
             const bool rec = cur < kSpecTiles;
             int mask = kAllPasses;
-            if (rec) {   // only the passes holding a stored value below theta change
+            if (rec) {   // only the passes holding an unclamped stored value below theta change
                 mask = 0;
 #pragma unroll
-                for (int p = 0; p < kPassesPerTile; ++p) mask |= (spec[kPassesPerTile * cur + p] < theta ? 1 : 0) << p;
+                for (int p = 0; p < kPassesPerTile; ++p) mask |= (shift_flags<float>(spec[kPassesPerTile * cur + p], theta) ? 1 : 0) << p;
                 if (!mask) continue;
             }
 #ifdef EWK_TIMING
@@ -1302,12 +1476,12 @@ __device__ void segment_stats(const SegSrc<RING>& v, const unsigned char* smem, 
             dbg[11] += __builtin_popcount(mask);
 #endif
             fix_tile(v, cur, T, rec ? spec[kSpecRun + cur] : -INFINITY, theta, smem, scr, tile, lane, lo, cref, s1,
-                     s2, mask);
+                     s2, mask, rec && ((shifted >> cur) & 1));
         }
     }
     if (__ballot(nanp != nanp)) {   // NaN input: NaN statistics, NaN score (like the reference)
 #pragma unroll
-        for (int i = 0; i < 8; ++i) s1[i] = __builtin_nan("");
+        for (int i = 0; i < kSlots; ++i) s1[i] = __builtin_nan("");
     }
     EWK_TS(tq4);
     EWK_TADD(5, tq3, tq4);
@@ -1335,10 +1509,10 @@ __device__ void segment_stats_coop(const SegSrc<RING>& v, unsigned char* smem, f
     const int ntile = (T + 15) >> 4;
     const int nloc = ntile > wave ? (ntile - wave + WAVES - 1) / WAVES : 0;
     const int col = lane & 15;
-    double s1[8], s2[8];
-    float cref[8];
+    double s1[kSlots], s2[kSlots];
+    float cref[kSlots];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) { s1[i] = 0.0; s2[i] = 0.0; cref[i] = 0.0f; }
+    for (int i = 0; i < kSlots; ++i) { s1[i] = 0.0; s2[i] = 0.0; cref[i] = 0.0f; }
     float vmax = -INFINITY, vmin = INFINITY, nanp = 0.0f;
     // the wave's last tile stays in LDS (unclamped) until the segment max is known, so a
     // segment of <= WAVES tiles (T <= 128) is never recomputed; earlier tiles are clamped
@@ -1369,11 +1543,11 @@ __device__ void segment_stats_coop(const SegSrc<RING>& v, unsigned char* smem, f
             lds_order();
         }
         run = fmaxf(run, run2);
-        float c[8];
+        float c[kSlots];
         tile_dct(tile, s_dct, lane, c);
         if (lt == 0) {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) cref[i] = __shfl(c[i], lane & 48, 64);
+            for (int i = 0; i < kSlots; ++i) cref[i] = __shfl(c[i], lane & 48, 64);
         }
         stats_add(c, cref, tile_i * 16 + col < T, s1, s2);
         if (lane == 0 && rec) {   // tile-granular records (both passes recomputed when theta bites)
@@ -1400,11 +1574,11 @@ __device__ void segment_stats_coop(const SegSrc<RING>& v, unsigned char* smem, f
             clamp_store(tile, lane, h, l, theta);
             lds_order();
         }
-        float c[8];
+        float c[kSlots];
         tile_dct(tile, s_dct, lane, c);
         if (nloc == 1) {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) cref[i] = __shfl(c[i], lane & 48, 64);
+            for (int i = 0; i < kSlots; ++i) cref[i] = __shfl(c[i], lane & 48, 64);
         }
         stats_add(c, cref, tile_l * 16 + col < T, s1, s2);
         if (vmin < theta) {
@@ -1419,23 +1593,21 @@ __device__ void segment_stats_coop(const SegSrc<RING>& v, unsigned char* smem, f
     }
     if (__ballot(nanp != nanp)) {   // NaN input (segment_stats): the combined sums go NaN
 #pragma unroll
-        for (int i = 0; i < 8; ++i) s1[i] = __builtin_nan("");
+        for (int i = 0; i < kSlots; ++i) s1[i] = __builtin_nan("");
     }
     // this wave's per-coefficient (s1, s2, cref) -> its scratch, as doubles [coef][3]
     double* pd = reinterpret_cast<double*>(scr);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) { s1[i] = row_sum_d(s1[i]); s2[i] = row_sum_d(s2[i]); }
+    for (int i = 0; i < kSlots; ++i) { s1[i] = row_sum_d(s1[i]); s2[i] = row_sum_d(s2[i]); }
     if (col == 15) {
         const int h = lane >> 4;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int k = 4 * h + r;
             pd[3 * k] = s1[r]; pd[3 * k + 1] = s2[r]; pd[3 * k + 2] = (double)cref[r];
-            if (h == 0) {
-                const int k2 = 16 + r;
-                pd[3 * k2] = s1[4 + r]; pd[3 * k2 + 1] = s2[4 + r]; pd[3 * k2 + 2] = (double)cref[4 + r];
-            }
         }
+        const int k2 = 16 + h;   // slot 4 of row h: coefficient 16 + h
+        pd[3 * k2] = s1[4]; pd[3 * k2 + 1] = s2[4]; pd[3 * k2 + 2] = (double)cref[4];
     }
     __syncthreads();
 #ifdef EWK_COOP_DEBUG
@@ -1795,7 +1967,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_score_f32(const Tables* __res
         EWK_TS(tw1);
         EWK_TADD(0, tw0, tw1);
 
-        double st1[8], st2[8];
+        double st1[kSlots], st2[kSlots];
         float theta_s;
         segment_stats(v, smem, scr, tile, spec, lane, lo, st1, st2, theta_s, wc, nx EWK_DBG_ARG);
         EWK_TS(tw2);

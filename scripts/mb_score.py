@@ -36,7 +36,7 @@ print(f"{lib:28s} L={fixed or 'ragged'} {ms:8.3f} ms  {frames/ms/1e6:7.3f} Gfram
 import ctypes
 lib = ctypes.CDLL(os.environ.get("EWK_LIB") or os.path.join(ROOT, "easywakeword_amd", "libewk.so"))
 if hasattr(lib, "ewk_debug_timing"):   # -DEWK_TIMING builds (easywakeword_amd/libewk_timing.so)
-    buf = (ctypes.c_ulonglong * 20)()
+    buf = (ctypes.c_ulonglong * 24)()   # kDbgN (ewk_mfcc.hip)
     lib.ewk_debug_timing(buf)      # reset
     e.profile(False)
     step(); torch.cuda.synchronize()
@@ -49,6 +49,15 @@ if hasattr(lib, "ewk_debug_timing"):   # -DEWK_TIMING builds (easywakeword_amd/l
           ", ".join(f"{n}={buf[i] / segs:,.0f} ({100.0 * buf[i] / max(1, tot):.1f}%)" for i, n in enumerate(names)) +
           f"; recomputed tiles/segment={(buf[10] & 0xffff) / segs:.3f} passes/segment={buf[11] / segs:.3f} "
           f"parked fixes/segment={(buf[10] >> 16) / segs:.3f}")
+    # top_db shift: a tile that holds a clamped entry runs its DCT with the mask DCT, then the shift
+    # sums and the pass minima (timed together: the mask phase); a plain tile's DCT is timed too
+    if buf[20] and buf[23]:
+        mphase, plain = buf[21] / buf[20], buf[22] / buf[23]
+        print(f"  masked tiles/segment={buf[20] / segs:.3f} ({100.0 * buf[20] / (buf[20] + buf[23]):.1f} % of tiles); "
+              f"mask phase (DCT + mask DCT + sums + minima) {mphase:,.0f} cycles per masked tile = "
+              f"{buf[21] / segs:,.0f} per segment ({100.0 * buf[21] / max(1, tot):.2f}%); plain DCT {plain:,.0f} cycles per "
+              f"other tile; the mask's share of it {(mphase - plain) * buf[20] / segs:,.0f} per segment "
+              f"({100.0 * (mphase - plain) * buf[20] / max(1, tot):.2f}%)")
     if buf[19]:   # frame-pass sub-phases (first-pass passes only)
         sub = ["window+DFT16a", "twiddle", "transposes", "DFT16b", "untangle+power", "mel+log", "tile write+stage"]
         print(f"  per frame pass ({buf[19] / waves:,.0f} per wave): " +

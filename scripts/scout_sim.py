@@ -5,6 +5,12 @@ For segments of the bench's ragged recipe (bench.make_segments on the CPU) it co
 heuristic, replays the speculative clamp (running max - 80 dB, self-clamp included) and
 counts the tiles and 8-frame passes the kernel would recompute.  Usage:
     python scripts/scout_sim.py [n_segments] [fixed_len]
+
+The "shift rule" lines replay the kernel's rule (csrc/ewk_topdb_shift.h) on the current scout
+order: a tile's clamped entries move up with the clamp inside the statistics, so a tile is
+recomputed only if one of its unclamped stored values lies between its own clamp and the final
+threshold.  They also give the share of tiles that hold a clamped entry (the tiles that pay for
+the mask DCT) and break the counts down per segment kind of the bench recipe.
 """
 import os
 import sys
@@ -75,6 +81,61 @@ def heuristics(y, ntile):
     return h
 
 
+KINDS = {0: "word", 1: "word", 2: "tone 880 Hz", 3: "noise burst"}
+
+
+def bench_kinds(n, seed=1234):
+    """The segment kinds bench.make_segments draws (same generator, same draws)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    rng.integers(6400, 33600 + 1, n)
+    rng.uniform(1e-4, 5e-3, n)
+    rng.uniform(0.2, 3.0, n)
+    return rng.integers(0, 4, n)
+
+
+def scout_order(y, ntile):
+    """The kernel's processing order: loudest first by the 4 x 64-sample scout, ties by index."""
+    e = [float((sample_rows(y, t, 4, 64, 640, 64).astype(np.float32) ** 2).sum()) for t in range(ntile)]
+    return sorted(range(ntile), key=lambda t: (-e[t], t))
+
+
+def replay_rules(L, order):
+    """Replay the speculative clamp over the raw log-mel L [128, T] in tile order `order`.
+    Returns the counts of both rules: tiles / passes whose stored minimum is below the final
+    threshold (old), tiles / passes holding an unclamped stored value in (run_k, theta) (shift
+    rule), the tiles holding a clamped entry (masked) and the tiles after the first that raise
+    the max over their own stored values (late_self_clamps: they are re-clamped in place and
+    every earlier tile shifts), and the largest rise theta - run_k over the passes that hold a
+    clamped entry and are not recomputed (max_kept_rise: what the shift alone has to get right)."""
+    T = L.shape[1]
+    theta = L.max() - 80.0
+    run = -np.inf
+    out = {"old_tiles": 0, "old_passes": 0, "new_tiles": 0, "new_passes": 0, "masked": 0, "tiles": len(order),
+           "late_self_clamps": 0, "max_kept_rise": 0.0, "kept_partial": 0}
+    for t in order:
+        X = L[:, 16 * t:min(T, 16 * t + 16)]
+        out["late_self_clamps"] += bool(np.isfinite(run) and X.max() - 80.0 > run and X.min() < X.max() - 80.0)
+        run = max(run, X.max() - 80.0)
+        out["masked"] += bool(X.min() < run)
+        old = new = 0
+        for p in (0, 8):
+            P = X[:, p:p + 8]
+            if P.size == 0:
+                continue
+            old += bool(max(P.min(), run) < theta)
+            free = P[P > run]                      # the unclamped stored values
+            flag = bool(free.size and free.min() < theta)
+            new += flag
+            if not flag and P.min() < run:         # shifted, never recomputed
+                out["max_kept_rise"] = max(out["max_kept_rise"], float(theta - run))
+                out["kept_partial"] += bool(free.size and theta - run >= 1.0)   # mask neither empty nor full
+        out["old_tiles"] += old > 0
+        out["old_passes"] += old
+        out["new_tiles"] += new > 0
+        out["new_passes"] += new
+    return out
+
+
 POS = {}
 PARK = {}
 
@@ -107,6 +168,8 @@ def main():
     pcm = pcm.numpy()
     tot = {}
     n_tiles = 0
+    kinds = bench_kinds(n)
+    rules = {}
     for i in range(n):
         y = pcm[offsets[i]:offsets[i] + lengths[i]].astype(np.float32)
         L = log_mel_raw(y)
@@ -117,6 +180,12 @@ def main():
         tmin = np.array([L[:, 16 * t:min(T, 16 * t + 16)].min() for t in range(ntile)])
         pmin = [[L[:, p:min(T, p + 8)].min() if p < T else np.inf for p in (16 * t, 16 * t + 8)] for t in range(ntile)]
         hs = heuristics(y, ntile)
+        r = replay_rules(L, scout_order(y, ntile) if ntile > 1 else [0])
+        for key in ("all", KINDS[int(kinds[i])]):
+            acc = rules.setdefault(key, dict.fromkeys(r, 0) | {"segments": 0})
+            for name, val in r.items():
+                acc[name] = max(acc[name], val) if name == "max_kept_rise" else acc[name] + int(val)
+            acc["segments"] += 1
         hs["oracle (true tile max)"] = tmax
         hs["time order"] = -np.arange(ntile, dtype=float)
         # hybrid: the current scout's order, its top K re-ranked by the chunked Hann energy
@@ -159,6 +228,13 @@ def main():
     for name, (a, b) in tot.items():
         print(f"  {name:28s} recomputed tiles/segment {a / n:6.3f} ({100.0 * a / n_tiles:5.1f} % of tiles)  "
               f"passes/segment {b / n:6.3f}  positions {dict(sorted(POS.get(name, {}).items())[:6])}")
+    for key, acc in rules.items():
+        ns = max(1, acc["segments"])
+        print(f"  shift rule, {key:12s} ({acc['segments']} segments): stored min < theta "
+              f"{acc['old_tiles'] / ns:6.3f} tiles {acc['old_passes'] / ns:6.3f} passes/segment; "
+              f"unclamped value in (run_k, theta) {acc['new_tiles'] / ns:6.3f} tiles "
+              f"{acc['new_passes'] / ns:6.3f} passes/segment; "
+              f"tiles with a clamped entry {100.0 * acc['masked'] / max(1, acc['tiles']):5.1f} %")
     for key, (pa, fp, fr) in PARK.items():
         print(f"  {key}: parked tiles/segment {pa / n:6.3f}, fixes from parked {fp / n:6.3f}, "
               f"recomputed {fr / n:6.3f}")
