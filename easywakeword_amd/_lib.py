@@ -40,6 +40,8 @@ EWK_RING_I16 = 1
 EWK_SCORE_REQUIRE_TEMPLATE = 1
 EWK_SCORE_F32_CANDIDATES = 2
 EWK_COMPACT_APPEND = 1
+EWK_BANK_MAX_PER_WORD = 64
+EWK_BANK_MAX_TEMPLATES = 65536
 
 # Every symbol include/ewk.h declares (checked by tests/test_capi.py).
 EXPORTS = [
@@ -52,6 +54,8 @@ EXPORTS = [
     "ewk_profile_enable", "ewk_profile_read",
     "ewk_push_pcm16", "ewk_push_many_pcm16", "ewk_normalize_segments", "ewk_normalize_events",
     "ewk_decode_pcm16", "ewk_poll_lagged", "ewk_runtime_info", "ewk_reenter", "ewk_compact_positives",
+    "ewk_bank_set", "ewk_bank_from_pcm", "ewk_bank_clear", "ewk_bank_info", "ewk_bank_get",
+    "ewk_score_segments_bank", "ewk_score_segments_bank_device",
 ]
 
 
@@ -85,6 +89,16 @@ class EwkPositive(C.Structure):
 
 POSITIVE_DTYPE = np.dtype([("id", "<i8"), ("score", "<f8"), ("step", "<i8")])
 assert POSITIVE_DTYPE.itemsize == C.sizeof(EwkPositive)
+
+
+class EwkBankResult(C.Structure):
+    _fields_ = [("best_score", C.c_double), ("hit_mask", C.c_uint64), ("best_tmpl", C.c_int32),
+                ("match", C.c_uint8), ("rescored", C.c_uint8), ("pad", C.c_uint16)]
+
+
+BANK_RESULT_DTYPE = np.dtype([("best_score", "<f8"), ("hit_mask", "<u8"), ("best_tmpl", "<i4"),
+                              ("match", "u1"), ("rescored", "u1"), ("pad", "<u2")])
+assert BANK_RESULT_DTYPE.itemsize == C.sizeof(EwkBankResult)
 
 
 class EwkStreamState(C.Structure):
@@ -164,6 +178,15 @@ def load():
             "ewk_normalize_events": (C.c_int, [_P, C.POINTER(EwkEvent), C.c_int32, _P, C.c_int32]),
             "ewk_decode_pcm16": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int32]),
             "ewk_compact_positives": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int64, C.c_int64, _P, _P, C.c_int32, _P]),
+            "ewk_bank_set": (C.c_int, [_P, C.c_int32, _i32p, _fp, _fp, _dp]),
+            "ewk_bank_from_pcm": (C.c_int, [_P, C.c_int32, _i32p, _fp, C.c_int64, _i64p, _i32p, _dp]),
+            "ewk_bank_clear": (C.c_int, [_P]),
+            "ewk_bank_info": (C.c_int, [_P, _i32p, _i32p]),
+            "ewk_bank_get": (C.c_int, [_P, C.c_int32, _fp, _fp]),
+            "ewk_score_segments_bank": (C.c_int, [_P, _fp, C.c_int64, _i64p, _i32p, C.c_int32, _i32p,
+                                                  C.POINTER(EwkBankResult), _dp, C.c_int32, C.c_int32]),
+            "ewk_score_segments_bank_device": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_int32,
+                                                         C.c_int32, _P]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)

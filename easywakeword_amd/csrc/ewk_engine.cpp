@@ -105,6 +105,21 @@ struct ewk_engine {
     DevBuf<uint8_t> match;
     DevBuf<double> mean64, std64;
 
+    // template bank (ewk_bank.hip): host copy as set, device copy value-major per word
+    std::vector<float> bank_mean, bank_std;   // [K][20]
+    std::vector<int32_t> bank_first;          // [n_words + 1]; empty: no bank
+    std::vector<double> bank_thr;             // [n_words]
+    bool bank_thr_follow = false;             // thresholds follow cfg.similarity_threshold
+    int32_t bank_max_word = 0;
+    DevBuf<float> d_bank;                     // [K][kBankRow] (BankArgs::bank)
+    DevBuf<int32_t> d_bank_first;
+    DevBuf<double> d_bank_thr;
+    DevBuf<int32_t> bk_cnt, bk_seg, bk_len;   // the fp64 list of a bank scoring call
+    DevBuf<int64_t> bk_off;
+    DevBuf<int32_t> bk_word;                  // host-call staging
+    DevBuf<ewk_bank_result> bk_out;
+    DevBuf<double> bk_scores;
+
     // streaming
     void* d_ring = nullptr;         // float32 or int16 samples (cfg.ring_format)
     size_t ring_es = sizeof(float); // bytes per ring sample
@@ -323,6 +338,16 @@ void ewk_destroy(ewk_engine* e) {
     e->match.release();
     e->mean64.release();
     e->std64.release();
+    e->d_bank.release();
+    e->d_bank_first.release();
+    e->d_bank_thr.release();
+    e->bk_cnt.release();
+    e->bk_seg.release();
+    e->bk_len.release();
+    e->bk_off.release();
+    e->bk_word.release();
+    e->bk_out.release();
+    e->bk_scores.release();
     e->push_stage.release();
     (void)hipFree(e->d_ring);
     (void)hipFree(e->d_brms);
@@ -731,6 +756,277 @@ int ewk_template_from_pcm(ewk_engine* e, const float* pcm, int64_t n) {
     e->has_tmpl = had;
     if (rc) return rc;
     return ewk_set_template(e, m, sd);
+}
+
+// ---------------------------------------------------------------- template bank
+static_assert(sizeof(ewk_bank_result) == 24, "ewk_bank_result is 24 bytes (include/ewk.h)");
+static const char* kNoBank = "No reference word set. Call set_bank() first.";
+
+static int check_bank_layout(int32_t n_words, const int32_t* word_first) {
+    if (n_words < 1) return fail(EWK_EINVAL, "a bank needs at least one word");
+    if (n_words > EWK_BANK_MAX_TEMPLATES)
+        return fail(EWK_EINVAL, "a bank holds at most " + std::to_string(EWK_BANK_MAX_TEMPLATES) + " templates");
+    if (!word_first) return fail(EWK_EINVAL, "NULL argument");
+    if (word_first[0] != 0) return fail(EWK_EINVAL, "word_first[0] must be 0");
+    for (int32_t w = 0; w < n_words; ++w) {
+        const int64_t sz = (int64_t)word_first[w + 1] - word_first[w];
+        if (sz < 1 || sz > EWK_BANK_MAX_PER_WORD)
+            return fail(EWK_EINVAL, "word " + std::to_string(w) + " has " + std::to_string(sz) +
+                                        " templates (1.." + std::to_string(EWK_BANK_MAX_PER_WORD) + ")");
+        if (word_first[w + 1] > EWK_BANK_MAX_TEMPLATES)
+            return fail(EWK_EINVAL, "a bank holds at most " + std::to_string(EWK_BANK_MAX_TEMPLATES) + " templates");
+    }
+    return EWK_OK;
+}
+
+int ewk_bank_set(ewk_engine* e, int32_t n_words, const int32_t* word_first, const float* mean, const float* stdv,
+                 const double* thresholds) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    int rc = check_bank_layout(n_words, word_first);
+    if (rc) return rc;
+    if (!mean || !stdv) return fail(EWK_EINVAL, "NULL argument");
+    if (thresholds)
+        for (int32_t w = 0; w < n_words; ++w)
+            if (!(thresholds[w] == thresholds[w])) return fail(EWK_EINVAL, "threshold is NaN");
+    const int32_t K = word_first[n_words];
+    std::vector<float> dev((size_t)K * kBankRow);
+    int32_t max_word = 0;
+    for (int32_t w = 0; w < n_words; ++w) {
+        const int32_t f = word_first[w], s = word_first[w + 1] - f;
+        max_word = std::max(max_word, s);
+        float* base = dev.data() + (size_t)kBankRow * f;
+        for (int32_t j = 0; j < s; ++j) {
+            const float* m = mean + (size_t)(f + j) * NMFCC;
+            const float* sd = stdv + (size_t)(f + j) * NMFCC;
+            double am = 0.0, as = 0.0;   // the float32 self-dots, as ewk_set_template computes them
+            for (int c = 0; c < NMFCC; ++c) {
+                base[c * s + j] = m[c];
+                base[(NMFCC + c) * s + j] = sd[c];
+                const float pm = m[c] * m[c], ps = sd[c] * sd[c];
+                am += (double)pm;
+                as += (double)ps;
+            }
+            base[2 * NMFCC * s + j] = (float)am;
+            base[(2 * NMFCC + 1) * s + j] = (float)as;
+        }
+    }
+    std::vector<double> thr(n_words, e->cfg.similarity_threshold);
+    if (thresholds) thr.assign(thresholds, thresholds + n_words);
+    HIP_TRY(hipSetDevice(e->device));
+    // a bank scoring call may still read the old bank (its fp64 pass is asynchronous)
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(e->d_bank.reserve(dev.size()));
+    HIP_TRY(e->d_bank_first.reserve((size_t)n_words + 1));
+    HIP_TRY(e->d_bank_thr.reserve(n_words));
+    HIP_TRY(hipMemcpyAsync(e->d_bank.p, dev.data(), dev.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->d_bank_first.p, word_first, ((size_t)n_words + 1) * sizeof(int32_t),
+                           hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->d_bank_thr.p, thr.data(), n_words * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->bank_mean.assign(mean, mean + (size_t)K * NMFCC);
+    e->bank_std.assign(stdv, stdv + (size_t)K * NMFCC);
+    e->bank_first.assign(word_first, word_first + n_words + 1);
+    e->bank_thr = thr;
+    e->bank_thr_follow = thresholds == nullptr;
+    e->bank_max_word = max_word;
+    return EWK_OK;
+}
+
+int ewk_bank_from_pcm(ewk_engine* e, int32_t n_words, const int32_t* word_first, const float* pcm, int64_t n_pcm,
+                      const int64_t* offsets, const int32_t* lengths, const double* thresholds) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    int rc = check_bank_layout(n_words, word_first);
+    if (rc) return rc;
+    if (!pcm || !offsets || !lengths || n_pcm < 0) return fail(EWK_EINVAL, "NULL argument");
+    const int32_t K = word_first[n_words];
+    for (int32_t k = 0; k < K; ++k)
+        if (lengths[k] < 1) return fail(EWK_EINVAL, "template length must be in [1, 2^31)");
+    std::vector<float> m((size_t)K * NMFCC), sd((size_t)K * NMFCC);
+    const bool had = e->has_tmpl;
+    e->has_tmpl = false;   // compute stats only (as ewk_template_from_pcm)
+    rc = ewk_score_segments(e, pcm, n_pcm, offsets, lengths, K, m.data(), sd.data(), nullptr, nullptr,
+                            EWK_SCORE_F32_CANDIDATES);
+    e->has_tmpl = had;
+    if (rc) return rc;
+    return ewk_bank_set(e, n_words, word_first, m.data(), sd.data(), thresholds);
+}
+
+int ewk_bank_clear(ewk_engine* e) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    e->bank_first.clear();
+    e->bank_mean.clear();
+    e->bank_std.clear();
+    e->bank_thr.clear();
+    e->bank_max_word = 0;
+    return EWK_OK;
+}
+
+int ewk_bank_info(ewk_engine* e, int32_t* n_words, int32_t* n_templates) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    const bool has = !e->bank_first.empty();
+    if (n_words) *n_words = has ? (int32_t)e->bank_first.size() - 1 : 0;
+    if (n_templates) *n_templates = has ? e->bank_first.back() : 0;
+    return EWK_OK;
+}
+
+int ewk_bank_get(ewk_engine* e, int32_t tmpl, float* mean20, float* std20) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (e->bank_first.empty()) return fail(EWK_ENOTEMPLATE, kNoBank);
+    if (tmpl < 0 || tmpl >= e->bank_first.back()) return fail(EWK_EINVAL, "template index out of range");
+    if (mean20) memcpy(mean20, e->bank_mean.data() + (size_t)tmpl * NMFCC, NMFCC * sizeof(float));
+    if (std20) memcpy(std20, e->bank_std.data() + (size_t)tmpl * NMFCC, NMFCC * sizeof(float));
+    return EWK_OK;
+}
+
+// The three passes on `s` (device pointers): float32 statistics, bank scores + fp64 list,
+// then -- after reading the list count back -- the fp64 statistics of the listed segments and
+// their scores again.
+static int bank_score(ewk_engine* e, const float* d_pcm, const int64_t* d_off, const int32_t* d_len, int32_t n,
+                      const int32_t* d_word, ewk_bank_result* d_out, double* d_scores, int32_t stride, int32_t flags,
+                      hipStream_t s) {
+    HIP_TRY(reserve_rescore(e, n));
+    HIP_TRY(e->mean.reserve((size_t)n * NMFCC));
+    HIP_TRY(e->stdv.reserve((size_t)n * NMFCC));
+    HIP_TRY(e->bk_cnt.reserve(1));
+    HIP_TRY(e->bk_seg.reserve(n));
+    HIP_TRY(e->bk_off.reserve(n));
+    HIP_TRY(e->bk_len.reserve(n));
+    HIP_TRY(join_scoring(e, s));
+    if (e->bank_thr_follow && e->bank_thr[0] != e->cfg.similarity_threshold) {
+        std::fill(e->bank_thr.begin(), e->bank_thr.end(), e->cfg.similarity_threshold);
+        HIP_TRY(hipMemcpyAsync(e->d_bank_thr.p, e->bank_thr.data(), e->bank_thr.size() * sizeof(double),
+                               hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));   // (the copy reads bank_thr)
+    }
+    ScoreArgs a = base_args(e);
+    a.has_template = 0;   // pass 1: statistics only, nothing listed
+    a.rs_slots = nullptr;
+    a.pcm = d_pcm;
+    a.offsets = d_off;
+    a.lengths = d_len;
+    a.n_seg = n;
+    a.out_mean = e->mean.p;
+    a.out_std = e->stdv.p;
+    {
+        ProfScope ps(e, 0, s);
+        HIP_TRY(launch_score_f32(e->d_tab, a, 0, s));
+    }
+    BankArgs b;
+    memset(&b, 0, sizeof(b));
+    b.bank = e->d_bank.p;
+    b.word_first = e->d_bank_first.p;
+    b.thresholds = e->d_bank_thr.p;
+    b.n_words = (int32_t)e->bank_first.size() - 1;
+    b.max_word = e->bank_max_word;
+    b.mean = e->mean.p;
+    b.stdv = e->stdv.p;
+    b.offsets = d_off;
+    b.lengths = d_len;
+    b.word = d_word;
+    b.n = n;
+    b.out = d_out;
+    b.out_scores = d_scores;
+    b.stride = stride;
+    b.cand_f32 = (flags & EWK_SCORE_F32_CANDIDATES) ? 1 : 0;
+    b.rescore_margin = e->cfg.rescore_margin;
+    b.crit = rescore_criteria();
+    b.list_cnt = e->bk_cnt.p;
+    b.list_seg = e->bk_seg.p;
+    b.list_off = e->bk_off.p;
+    b.list_len = e->bk_len.p;
+    HIP_TRY(launch_bank_score(b, s));
+    int32_t listed = 0;
+    HIP_TRY(hipMemcpyAsync(&listed, e->bk_cnt.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (listed <= 0) return EWK_OK;
+    if (listed > n) return fail(EWK_EHIP, "bank list count out of range");
+    HIP_TRY(e->mean64.reserve((size_t)listed * NMFCC));
+    HIP_TRY(e->std64.reserve((size_t)listed * NMFCC));
+    // pass 3: the listed segments through the fp64 path (list_all, as ewk_score_segments_f64)
+    ScoreArgs f = base_args(e);
+    f.has_template = 0;
+    f.pcm = d_pcm;
+    f.offsets = e->bk_off.p;
+    f.lengths = e->bk_len.p;
+    f.n_seg = listed;
+    f.list_all = 1;
+    f.rs_slots = e->rs_slots.p;
+    f.out_mean64 = e->mean64.p;
+    f.out_std64 = e->std64.p;
+    {
+        ProfScope ps(e, 1, s);
+        HIP_TRY(launch_score_f32(e->d_tab, f, 0, s));
+        HIP_TRY(launch_rescore_linear(f, s));
+    }
+    b.mean = e->mean64.p;
+    b.stdv = e->std64.p;
+    b.n = listed;
+    HIP_TRY(launch_bank_rescore(b, s));
+    return EWK_OK;
+}
+
+static int check_bank_call(ewk_engine* e, int32_t n_seg, const void* out, const double* out_scores, int32_t stride) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (n_seg < 0) return fail(EWK_EINVAL, "n_seg must be >= 0");
+    if (e->bank_first.empty()) return fail(EWK_ENOTEMPLATE, kNoBank);
+    if (n_seg > 0 && !out) return fail(EWK_EINVAL, "NULL argument");
+    if (out_scores && stride < e->bank_max_word)
+        return fail(EWK_EINVAL, "stride " + std::to_string(stride) + " is smaller than the bank's largest word (" +
+                                    std::to_string(e->bank_max_word) + ")");
+    return EWK_OK;
+}
+
+int ewk_score_segments_bank_device(ewk_engine* e, const float* d_pcm, const int64_t* d_offsets,
+                                   const int32_t* d_lengths, int32_t n_seg, const int32_t* d_word,
+                                   ewk_bank_result* d_out, double* d_out_scores, int32_t stride, int32_t flags,
+                                   void* stream) {
+    int rc = check_bank_call(e, n_seg, d_out, d_out_scores, stride);
+    if (rc) return rc;
+    if (n_seg == 0) return EWK_OK;
+    if (!d_pcm || !d_offsets || !d_lengths) return fail(EWK_EINVAL, "NULL device pointer");
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = stream ? (hipStream_t)stream : e->stream;
+    return bank_score(e, d_pcm, d_offsets, d_lengths, n_seg, d_word, d_out, d_out_scores, stride, flags, s);
+}
+
+int ewk_score_segments_bank(ewk_engine* e, const float* pcm, int64_t n_pcm, const int64_t* offsets,
+                            const int32_t* lengths, int32_t n_seg, const int32_t* word, ewk_bank_result* out,
+                            double* out_scores, int32_t stride, int32_t flags) {
+    int rc = check_bank_call(e, n_seg, out, out_scores, stride);
+    if (rc) return rc;
+    if (n_pcm < 0) return fail(EWK_EINVAL, "negative size");
+    if (n_seg == 0) return EWK_OK;
+    if (!offsets || !lengths || (n_pcm > 0 && !pcm)) return fail(EWK_EINVAL, "NULL argument");
+    int32_t max_len = 0;
+    rc = check_segments(offsets, lengths, n_seg, n_pcm, &max_len);
+    if (rc) return rc;
+    const int32_t n_words = (int32_t)e->bank_first.size() - 1;
+    if (word)
+        for (int32_t i = 0; i < n_seg; ++i)
+            if (word[i] < 0 || word[i] >= n_words)
+                return fail(EWK_EINVAL, "word index " + std::to_string(word[i]) + " of segment " + std::to_string(i) +
+                                            " is outside [0, " + std::to_string(n_words) + ")");
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t n_sc = out_scores ? (size_t)n_seg * stride : 0;
+    HIP_TRY(e->pcm.reserve(std::max<int64_t>(n_pcm, 1)));
+    HIP_TRY(e->offsets.reserve(n_seg));
+    HIP_TRY(e->lengths.reserve(n_seg));
+    HIP_TRY(e->bk_word.reserve(n_seg));
+    HIP_TRY(e->bk_out.reserve(n_seg));
+    if (n_sc) HIP_TRY(e->bk_scores.reserve(n_sc));
+    hipStream_t s = e->stream;
+    HIP_TRY(join_scoring(e, s));
+    if (n_pcm > 0) HIP_TRY(hipMemcpyAsync(e->pcm.p, pcm, n_pcm * sizeof(float), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(e->offsets.p, offsets, n_seg * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(e->lengths.p, lengths, n_seg * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (word) HIP_TRY(hipMemcpyAsync(e->bk_word.p, word, n_seg * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    rc = bank_score(e, e->pcm.p, e->offsets.p, e->lengths.p, n_seg, word ? e->bk_word.p : nullptr, e->bk_out.p,
+                    n_sc ? e->bk_scores.p : nullptr, stride, flags, s);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, e->bk_out.p, n_seg * sizeof(ewk_bank_result), hipMemcpyDeviceToHost, s));
+    if (n_sc) HIP_TRY(hipMemcpyAsync(out_scores, e->bk_scores.p, n_sc * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return EWK_OK;
 }
 
 // ---------------------------------------------------------------- streaming path

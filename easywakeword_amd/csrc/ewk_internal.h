@@ -162,6 +162,48 @@ hipError_t launch_snapshot(const int32_t* src, int32_t* dst, hipStream_t s);   /
 hipError_t launch_bank_mirror(const int32_t* evc, const ewk_event* ev, uint32_t base0, int32_t cap, int32_t chunk,
                               unsigned char* host, hipStream_t s);
 
+// Template bank (ewk_bank.hip): every segment's MFCC statistics against the templates of one
+// word.  Pass 1 is launch_score_f32 without a template (statistics only), pass 2
+// launch_bank_score, pass 3 the list_all fp64 path on the listed segments followed by
+// launch_bank_rescore.
+struct RescoreCriteria {           // the scorer's vanishing-mean listing constants (ewk_mfcc.hip)
+    double tiny_mean, nan_a, nan_b;
+};
+RescoreCriteria rescore_criteria();
+constexpr int kBankRow = 2 * NMFCC + 2;   // floats per template: mean[20], std[20], uu_m, uu_s
+struct BankArgs {
+    // word w (s = its size) starts at bank + kBankRow * word_first[w] and is value-major:
+    // value c of its template j at [c * s + j] -- lane j's loads are contiguous across its group
+    const float* bank;
+    const int32_t* word_first;    // [n_words + 1]
+    const double* thresholds;     // [n_words]
+    int32_t n_words;
+    int32_t max_word;             // the bank's largest word: a segment takes the next power of two lanes
+    int32_t group_log2;           // (set by the launchers) log2 of that group width
+    // statistics [.][20]: float32 by segment (launch_bank_score), float64 by list position
+    // (launch_bank_rescore)
+    const void* mean;
+    const void* stdv;
+    const int64_t* offsets;       // by segment (launch_bank_score only)
+    const int32_t* lengths;
+    const int32_t* word;          // by segment; nullptr: word 0
+    int32_t n;                    // segments (launch_bank_score) / listed segments (launch_bank_rescore)
+    ewk_bank_result* out;         // by segment
+    double* out_scores;           // nullptr or [n][stride]
+    int32_t stride;
+    int32_t cand_f32;
+    double rescore_margin;
+    RescoreCriteria crit;
+    // segments the float32 statistics cannot decide: count, then (segment, offset, length) per
+    // entry in arrival order (any order gives the same results: pass 3 writes by segment)
+    int32_t* list_cnt;
+    int32_t* list_seg;
+    int64_t* list_off;
+    int32_t* list_len;
+};
+hipError_t launch_bank_score(const BankArgs& a, hipStream_t s);     // (zeroes *list_cnt first)
+hipError_t launch_bank_rescore(const BankArgs& a, hipStream_t s);
+
 constexpr int kScoreGridMax = 256;   // one resident workgroup wave of the grid
 constexpr int kScoreGridRing = 256;                     // ring-mode grid (device-side event count)
 int score_grid(int n_seg, int ring_mode);

@@ -49,7 +49,8 @@
 #include <math.h>
 
 #include "ewk_internal.h"
-#include "ewk_db64.h"   // (the fp64 re-score's 10 log10, ewk_rescore.h)
+#include "ewk_score.h"  // the score arithmetic and listing constants shared with ewk_bank.hip
+#include "ewk_db64.h"  // (the fp64 re-score's 10 log10, ewk_rescore.h)
 #include "ewk_topdb_shift.h"
 
 // s_setprio 1 over the frame-pass LDS phases (window, transposes, mel): -0.4 %
@@ -171,7 +172,7 @@ constexpr int W_BYTES = W_SPEC + (kSpecOrder + kSpecTiles) * 4;
 static_assert(W_BYTES % 16 == 0 && kSpecTiles <= 64, "per-wave LDS carve; one bit per recorded tile");
 constexpr int L_WG = L_SHARED_END + WAVES * W_BYTES;    // ring mode: segment index + per-wave log-mel max/min
 constexpr int LDS_BYTES = L_WG + 16 + 8 * WAVES;
-constexpr int kRescoreFrames = 16;
+// (kRescoreFrames and kTinyStd: ewk_score.h)
 // |mean vector| below which the fp64 path decides (round 5: 32, was 64).  Evidence for 32: the
 // float32 score error of streaming events is <= 1.2e-5 above |mean| 32 (profiles/r05_v26_mean_err.txt)
 // and 600 segments of four other loud recipes with oracle |mean| in [32, 64) score within 8.6e-6
@@ -192,8 +193,6 @@ constexpr double kTinyMean = EWK_TINY_MEAN;
 #endif
 constexpr double kNanMarginA = EWK_NAN_MARGIN_A;
 constexpr double kNanMarginB = 0.05;
-constexpr double kTinyStd = 20.0;   // |std vector| below which the fp64 path decides (bench batch >= 24.8,
-                                    // streaming events >= 32.5: scripts/std_norm_dist.py)
 static_assert(LDS_BYTES <= 160 * 1024, "the workgroup must fit a CU's LDS");
 static_assert(16 % kFPP == 0, "passes must tile the 16-frame log-mel tile");
 
@@ -1642,80 +1641,6 @@ __device__ void segment_stats_coop(const SegSrc<RING>& v, unsigned char* smem, f
     }
 }
 
-// ---- the score, exactly as WordMatcher.calculate_similarity evaluates it --------
-// (wakeword.py:611-625 with scipy 1.15 `correlation`: dist = clip(1 - uv/sqrt(uu*vv), 0, 2)).
-// The template u is float32 (librosa.load -> float32 MFCCs).  numpy's dot of two
-// float32 vectors is float(sum_double(float(a*b))) (cblas_sdot's scalar path for
-// n = 20, verified bit for bit against np.dot); a float32 x float64 or float64 dot
-// is a float64 dot.  Two candidate dtypes occur in the reference:
-//   float64 (streaming: SoundBuffer slices, wakeword.py:428, 509-513): uu is a
-//     float32 dot, uv / vv float64, the rest float64;
-//   float32 (WordMatcher on float32 audio): every dot float32 and, under NumPy 2
-//     scalar promotion, every following operation float32.
-__device__ __forceinline__ float sdot20(const float* a, const float* b) {
-#pragma clang fp contract(off)
-    double acc = 0.0;
-    for (int i = 0; i < NMFCC; ++i) acc += (double)(a[i] * b[i]);
-    return (float)acc;
-}
-
-template <typename T>
-__device__ __forceinline__ double ddot20(const float* a, const T* b) {
-#pragma clang fp contract(off)
-    double acc = 0.0;
-    for (int i = 0; i < NMFCC; ++i) acc += (double)a[i] * (double)b[i];
-    return acc;
-}
-
-template <typename T>
-__device__ __forceinline__ double ddot20s(const T* a) {
-#pragma clang fp contract(off)
-    double acc = 0.0;
-    for (int i = 0; i < NMFCC; ++i) acc += (double)a[i] * (double)a[i];
-    return acc;
-}
-
-__device__ __forceinline__ double clip02(double d) {
-    if (d < 0.0) return 0.0;
-    if (d > 2.0) return 2.0;
-    return d;   // NaN passes through (np.clip)
-}
-
-__device__ __forceinline__ float clip02f(float d) {
-    if (d < 0.0f) return 0.0f;
-    if (d > 2.0f) return 2.0f;
-    return d;
-}
-
-// Candidate stats in float64 (the streaming dtype).
-__device__ double score_f64cand(const float* tm, const float* ts, const double* cm, const double* cs) {
-#pragma clang fp contract(off)
-    const double uu_m = (double)sdot20(tm, tm), uu_s = (double)sdot20(ts, ts);
-    const double sm = 1.0 - clip02(1.0 - ddot20(tm, cm) / sqrt(uu_m * ddot20s(cm)));
-    const double ss = 1.0 - clip02(1.0 - ddot20(ts, cs) / sqrt(uu_s * ddot20s(cs)));
-    const double combined = sm * 0.7 + ss * 0.3;
-    const double percent = combined * 100.0;
-    return pow(percent, 1.5) / 10.0;   // (100**0.5) == 10.0 exactly
-}
-
-// Candidate stats in float32 (WordMatcher on float32 audio): float32 arithmetic.
-__device__ double score_f32cand(const float* tm, const float* ts, const float* cm, const float* cs) {
-#pragma clang fp contract(off)
-    float sim[2];
-    for (int k = 0; k < 2; ++k) {
-        const float* u = k ? ts : tm;
-        const float* v = k ? cs : cm;
-        const float uu = sdot20(u, u), vv = sdot20(v, v), uv = sdot20(u, v);
-        const float prod = uu * vv;                       // float32 * float32
-        const float root = (float)sqrt((double)prod);      // math.sqrt, back to float32 (NEP 50)
-        const float dist = clip02f(1.0f - uv / root);
-        sim[k] = 1.0f - dist;
-    }
-    const float combined = sim[0] * 0.7f + sim[1] * 0.3f;
-    const float percent = combined * 100.0f;
-    return (double)(powf(percent, 1.5f) / 10.0f);
-}
-
 
 // Fast-path finishes (the fp64 re-score keeps the reference's exact pow / sequential dots).
 __device__ __forceinline__ double score_f64_finish(double uu_m, double uu_s, double uv_m, double vv_m, double uv_s,
@@ -2192,6 +2117,9 @@ hipError_t launch_rescore_ring(const ScoreArgs& a, hipStream_t s) {
     else hipLaunchKernelGGL(k_rescore_ring<1>, dim3(kScoreGridRing), dim3(64 * RS_NW), RS_LDS, s, a);
     return hipGetLastError();
 }
+
+// The vanishing-mean listing constants above, for the template bank's listing rule.
+RescoreCriteria rescore_criteria() { return {kTinyMean, kNanMarginA, kNanMarginB}; }
 
 }  // namespace ewk
 

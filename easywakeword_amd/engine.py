@@ -26,6 +26,46 @@ def _f32(audio) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def _pack(segs):
+    """Ragged float32 arrays -> (pcm, offsets int64, lengths int32)."""
+    n = len(segs)
+    lengths = np.array([len(s) for s in segs], dtype=np.int32)
+    offsets = np.zeros(n, dtype=np.int64)
+    if n:
+        offsets[1:] = np.cumsum(lengths[:-1], dtype=np.int64)
+    pcm = np.ascontiguousarray(np.concatenate(segs) if n else np.zeros(0, np.float32), dtype=np.float32)
+    return pcm, offsets, lengths
+
+
+def bank_layout(words, thresholds=None):
+    """Layout of a template bank (include/ewk.h): `words` is a list of words, each a sequence of
+    1..64 templates (only the lengths are read here).  Returns (word_first int32[n_words + 1],
+    thresholds float64[n_words] or None); word w is templates word_first[w] .. word_first[w + 1]
+    - 1.  Raises ValueError for an empty bank or word, a word over EWK_BANK_MAX_PER_WORD
+    templates, a bank over EWK_BANK_MAX_TEMPLATES or a `thresholds` of another length."""
+    sizes = [len(w) for w in words]
+    if not sizes:
+        raise ValueError("a bank needs at least one word")
+    for w, s in enumerate(sizes):
+        if s < 1:
+            raise ValueError(f"word {w} has no templates")
+        if s > _lib.EWK_BANK_MAX_PER_WORD:
+            raise ValueError(f"word {w} has {s} templates; at most {_lib.EWK_BANK_MAX_PER_WORD} per word")
+    total = int(sum(sizes))
+    if total > _lib.EWK_BANK_MAX_TEMPLATES:
+        raise ValueError(f"bank has {total} templates; at most {_lib.EWK_BANK_MAX_TEMPLATES}")
+    word_first = np.zeros(len(sizes) + 1, dtype=np.int32)
+    word_first[1:] = np.cumsum(sizes)
+    thr = None
+    if thresholds is not None:
+        thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+        if thr.size != len(sizes):
+            raise ValueError(f"{thr.size} thresholds for {len(sizes)} words")
+        if np.isnan(thr).any():
+            raise ValueError("threshold is NaN")
+    return word_first, thr
+
+
 class Engine:
     """Owns one ewk_engine on `gpu` (scorer-only unless n_streams > 0)."""
 
@@ -156,6 +196,96 @@ class Engine:
                                                _lib.i32ptr(lengths), n, _lib.dptr(mean), _lib.dptr(std),
                                                _lib.dptr(score), self._flags(False, f32)))
         return mean, std, score
+
+    # -- template bank: many references per segment -------------------------------
+    @staticmethod
+    def _thr_ptr(thr):
+        return _lib.dptr(thr) if thr is not None else None
+
+    def set_bank(self, words, thresholds=None) -> None:
+        """`words`: a list of words, each a list of (mean[20], std[20]) templates (1..64 per
+        word); `thresholds`: one per word, or None for the engine's threshold."""
+        word_first, thr = bank_layout(words, thresholds)
+        mean = np.zeros((int(word_first[-1]), N_MFCC), np.float32)
+        std = np.zeros_like(mean)
+        k = 0
+        for w in words:
+            for m, s in w:
+                m, s = _f32(m), _f32(s)
+                if m.size != N_MFCC or s.size != N_MFCC:
+                    raise ValueError(f"template must be {N_MFCC} means and {N_MFCC} stds")
+                mean[k], std[k] = m, s
+                k += 1
+        check(self._lib.ewk_bank_set(self._h, len(word_first) - 1, _lib.i32ptr(word_first), _lib.fptr(mean),
+                                     _lib.fptr(std), self._thr_ptr(thr)))
+        self._bank_max_word = int(np.diff(word_first).max())
+
+    def bank_from_pcm(self, words_audio, thresholds=None) -> None:
+        """set_bank with every template computed from audio (as template_from_pcm):
+        `words_audio` is a list of words, each a list of 1-D arrays."""
+        word_first, thr = bank_layout(words_audio, thresholds)
+        segs = [_f32(a) for w in words_audio for a in w]
+        if any(len(s) == 0 for s in segs):
+            raise ValueError("template length must be in [1, 2^31)")
+        pcm, offsets, lengths = _pack(segs)
+        check(self._lib.ewk_bank_from_pcm(self._h, len(word_first) - 1, _lib.i32ptr(word_first), _lib.fptr(pcm),
+                                          len(pcm), _lib.i64ptr(offsets), _lib.i32ptr(lengths), self._thr_ptr(thr)))
+        self._bank_max_word = int(np.diff(word_first).max())
+
+    def clear_bank(self) -> None:
+        check(self._lib.ewk_bank_clear(self._h))
+        self._bank_max_word = 0
+
+    def bank_info(self) -> Tuple[int, int]:
+        """(number of words, number of templates); (0, 0) without a bank."""
+        nw, nt = C.c_int32(0), C.c_int32(0)
+        check(self._lib.ewk_bank_info(self._h, C.byref(nw), C.byref(nt)))
+        return int(nw.value), int(nt.value)
+
+    def bank_template(self, tmpl: int) -> Tuple[np.ndarray, np.ndarray]:
+        m = np.zeros(N_MFCC, np.float32)
+        s = np.zeros(N_MFCC, np.float32)
+        check(self._lib.ewk_bank_get(self._h, int(tmpl), _lib.fptr(m), _lib.fptr(s)))
+        return m, s
+
+    def score_bank(self, segments, word=None, candidate_dtype: str = "auto", all_scores: bool = False):
+        """Score segment i against every template of word[i] (word None: word 0).  Returns a
+        structured array (_lib.BANK_RESULT_DTYPE: best_score, hit_mask, best_tmpl, match,
+        rescored) and, with all_scores=True, also scores[n, stride] float64: the score against
+        template j of the segment's word, NaN past the word's size (stride = the bank's largest word)."""
+        if candidate_dtype == "auto":
+            f32 = all(np.asarray(s).dtype == np.float32 for s in segments) and len(segments) > 0
+        else:
+            f32 = np.dtype(candidate_dtype) == np.float32
+        pcm, offsets, lengths = _pack([_f32(s) for s in segments])
+        n = len(lengths)
+        wp = None
+        if word is not None:
+            word = np.ascontiguousarray(word, dtype=np.int32).reshape(-1)
+            if word.size != n:
+                raise ValueError(f"{word.size} word indices for {n} segments")
+            wp = _lib.i32ptr(word)
+        out = np.zeros(n, dtype=_lib.BANK_RESULT_DTYPE)
+        stride = getattr(self, "_bank_max_word", 0) or _lib.EWK_BANK_MAX_PER_WORD
+        scores = np.full((n, stride), np.nan, np.float64) if all_scores else None
+        check(self._lib.ewk_score_segments_bank(self._h, _lib.fptr(pcm), len(pcm), _lib.i64ptr(offsets),
+                                                _lib.i32ptr(lengths), n, wp,
+                                                out.ctypes.data_as(C.POINTER(_lib.EwkBankResult)),
+                                                _lib.dptr(scores) if all_scores else None, stride,
+                                                self._flags(False, f32)))
+        return (out, scores) if all_scores else out
+
+    def score_bank_device(self, pcm_ptr: int, offsets_ptr: int, lengths_ptr: int, n: int, word_ptr: int,
+                          out_ptr: int, scores_ptr: int = 0, stride: int = 0, stream: int = 0,
+                          f32_candidates: bool = False) -> None:
+        """Device-resident score_bank (e.g. torch tensor data_ptr()s): out_ptr holds n
+        ewk_bank_result records (24 bytes each), scores_ptr (0: none) n * stride float64.
+        Synchronises `stream` once, after the float32 pass (include/ewk.h)."""
+        check(self._lib.ewk_score_segments_bank_device(self._h, C.c_void_p(pcm_ptr), C.c_void_p(offsets_ptr),
+                                                       C.c_void_p(lengths_ptr), int(n), C.c_void_p(word_ptr or None),
+                                                       C.c_void_p(out_ptr or None), C.c_void_p(scores_ptr or None),
+                                                       int(stride), self._flags(False, f32_candidates),
+                                                       C.c_void_p(stream or None)))
 
     def normalize(self, segments) -> list:
         """Level-3 pre-processing of each segment on the GPU (wakeword.py:1019-1025):

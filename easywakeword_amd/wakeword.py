@@ -59,7 +59,12 @@ class WordMatcher:
     threshold is re-scored in float64 on the device, so decisions are exact).
 
     A matcher built with ``engine=`` shares that engine; ``matches(audio, threshold)``
-    applies its threshold for that call only and restores the engine's afterwards."""
+    applies its threshold for that call only and restores the engine's afterwards.
+
+    ``set_references`` / ``load_references_from_files`` take several recordings of the word
+    (the engine's template bank): the similarity is then the best score over them and a
+    candidate matches when any of them reaches the threshold.  ``set_reference`` returns to
+    one reference."""
 
     def __init__(self, sample_rate: int = FREQUENCY, gpu: int = 0, engine: Optional[Engine] = None) -> None:
         if sample_rate != FREQUENCY:
@@ -69,6 +74,7 @@ class WordMatcher:
         self.reference_mfcc_std: Optional[np.ndarray] = None
         self.reference_word: Optional[str] = None
         self._engine = engine if engine is not None else Engine(gpu=gpu)
+        self._n_references = 0   # > 0: the engine's template bank holds that many references
 
     @property
     def engine(self) -> Engine:
@@ -86,9 +92,40 @@ class WordMatcher:
         self.reference_word = word_name
         self._engine.template_from_pcm(audio)
         self.reference_mfcc_mean, self.reference_mfcc_std = self._engine.get_template()
+        if self._n_references:
+            self._engine.clear_bank()
+            self._n_references = 0
 
     def load_reference_from_file(self, filepath: str, word_name: str = "target") -> None:
         self.set_reference(_audio.load_wav(filepath, sr=self.sample_rate), word_name)
+
+    def set_references(self, audios, word_name: str = "target") -> None:
+        """Several recordings of the word (1..64): one word of the engine's template bank.
+        reference_mfcc_mean / reference_mfcc_std (and the engine's single template) are
+        those of the first."""
+        audios = list(audios)
+        self._engine.bank_from_pcm([audios])
+        self._n_references = len(audios)
+        self.reference_word = word_name
+        self.reference_mfcc_mean, self.reference_mfcc_std = self._engine.bank_template(0)
+        self._engine.set_template(self.reference_mfcc_mean, self.reference_mfcc_std)
+
+    def load_references_from_files(self, filepaths, word_name: str = "target") -> None:
+        self.set_references([_audio.load_wav(p, sr=self.sample_rate) for p in filepaths], word_name)
+
+    def score_bank(self, segments, threshold: float = 75.0) -> np.ndarray:
+        """The bank results (easywakeword_amd._lib.BANK_RESULT_DTYPE) of `segments` against
+        the references of set_references, at `threshold` for this call only."""
+        if not self._n_references:
+            raise ValueError("No reference word set. Call set_references() first.")
+        old = self._engine.config.similarity_threshold
+        if float(threshold) == old:
+            return self._engine.score_bank(segments)
+        self._engine.set_threshold(threshold)
+        try:
+            return self._engine.score_bank(segments)
+        finally:
+            self._engine.set_threshold(old)
 
     def _sync_template(self) -> None:
         if self.reference_mfcc_mean is None:
@@ -107,12 +144,17 @@ class WordMatcher:
             return False
 
     def calculate_similarity(self, audio: np.ndarray) -> float:
+        if self._n_references:
+            return float(self._engine.score_bank([audio])["best_score"][0])
         self._sync_template()
         _, _, score, _ = self._engine.score([audio])
         return float(score[0])
 
     def _score_at(self, segments, threshold: float):
         """Score with `threshold` for this call only (a shared engine keeps its own)."""
+        if self._n_references:   # any reference >= threshold, best score over the references
+            res = self.score_bank(segments, threshold)
+            return None, None, res["best_score"].copy(), res["match"].astype(bool)
         self._sync_template()
         old = self._engine.config.similarity_threshold
         if float(threshold) == old:
@@ -217,7 +259,7 @@ class WakeWord:
     def __init__(
         self,
         textword: str,
-        wavword: str,
+        wavword: Union[str, list, tuple],
         numberofwords: int = 2,
         timeout: int = 30,
         callback: Optional[Callable[[str], None]] = None,
@@ -261,7 +303,13 @@ class WakeWord:
             raise ValueError("post_speech_silence must be positive")
 
         self.textword = textword.lower().strip()
-        self.wavword = wavword
+        # several recordings of the word: the first is the stream engine's template (and the
+        # one the speech durations are analysed from); events are decided against all of them
+        self._wavwords = [wavword] if isinstance(wavword, (str, bytes)) or hasattr(wavword, "__fspath__") \
+            else list(wavword)
+        if not self._wavwords:
+            raise ValueError("wavword must name at least one reference file")
+        self.wavword = self._wavwords[0]
         self.numberofwords = numberofwords
         self.timeout = timeout
         self.callback = callback
@@ -413,7 +461,10 @@ class WakeWord:
         if self._matcher is None:
             # its own scorer engine: matches(threshold=...) must not move the stream's threshold
             self._matcher = WordMatcher(sample_rate=FREQUENCY, gpu=self._gpu)
-            self._matcher.load_reference_from_file(self.wavword, self.textword)
+            if len(self._wavwords) > 1:
+                self._matcher.load_references_from_files(self._wavwords, self.textword)
+            else:
+                self._matcher.load_reference_from_file(self.wavword, self.textword)
             self._sound_buffer.engine.set_template(self._matcher.reference_mfcc_mean,
                                                    self._matcher.reference_mfcc_std)
 
@@ -448,9 +499,18 @@ class WakeWord:
         for ev in events:
             if ev["flags"] & 1:   # too long: skipped (wakeword.py:1113-1118)
                 continue
-            self._log(f"MFCC similarity: {ev['score']:.1f}%")
-            if not ev["match"]:
-                continue
+            if len(self._wavwords) > 1:
+                # the stream scored reference 0 only: decide against every reference on the
+                # matcher's scorer (float64 candidates, as the stream's segments are)
+                audio = self._sound_buffer.engine.read_segment(0, int(ev["ring_start"]), int(ev["length"]))
+                res = self._matcher.score_bank([audio.astype(np.float64)], self.similarity_threshold)
+                self._log(f"MFCC similarity: {res['best_score'][0]:.1f}% (reference {res['best_tmpl'][0]})")
+                if not res["match"][0]:
+                    continue
+            else:
+                self._log(f"MFCC similarity: {ev['score']:.1f}%")
+                if not ev["match"]:
+                    continue
             if self._confirm is None:
                 return self.textword
             audio = self._sound_buffer.engine.read_segment(0, int(ev["ring_start"]), int(ev["length"]))

@@ -178,6 +178,60 @@ int ewk_score_segments_f64(ewk_engine* e, const float* pcm, int64_t n_pcm,
                            const int64_t* offsets, const int32_t* lengths, int32_t n_seg,
                            double* out_mean, double* out_std, double* out_score, int32_t flags);
 
+/* ---- level 2 against many references: the template bank ----------------------- */
+/* A bank is a list of words; a word is 1..EWK_BANK_MAX_PER_WORD templates (several
+ * recordings of it) stored contiguously, with one threshold.  Each segment of a batch is
+ * scored against every template of one word (word[i], or word 0 without an index array):
+ * the MFCC statistics are computed once per segment and every further template costs one
+ * cosine score on them.  The engine's single template and every entry point above are
+ * unaffected by a bank. */
+#define EWK_BANK_MAX_PER_WORD 64
+#define EWK_BANK_MAX_TEMPLATES 65536
+typedef struct ewk_bank_result {   /* 24 bytes */
+    double best_score;            /* max over the word's templates ignoring NaN; NaN when all are NaN */
+    uint64_t hit_mask;            /* bit j: template word_first[w] + j scored >= the word's threshold */
+    int32_t best_tmpl;            /* bank-wide index of best_score's template (lowest on ties), -1 when all NaN */
+    uint8_t match;                /* hit_mask != 0 */
+    uint8_t rescored;             /* scores of this segment come from the fp64 statistics */
+    uint16_t pad;
+} ewk_bank_result;
+
+/* Word w is templates word_first[w] .. word_first[w + 1] - 1 of mean / stdv ([K][20] float32,
+ * K = word_first[n_words], word_first[0] = 0).  thresholds: one per word, or NULL: every word
+ * uses the engine's similarity threshold (ewk_set_similarity_threshold) as it stands at each
+ * scoring call.  Replaces any bank already set (waits for the engine's stream first; a bank
+ * scoring call still running on a caller's stream must have finished). */
+int ewk_bank_set(ewk_engine* e, int32_t n_words, const int32_t* word_first, const float* mean,
+                 const float* stdv, const double* thresholds);
+/* The same with template k computed from pcm[offsets[k] : offsets[k] + lengths[k]] as
+ * ewk_template_from_pcm computes its template. */
+int ewk_bank_from_pcm(ewk_engine* e, int32_t n_words, const int32_t* word_first, const float* pcm,
+                      int64_t n_pcm, const int64_t* offsets, const int32_t* lengths,
+                      const double* thresholds);
+int ewk_bank_clear(ewk_engine* e);
+/* 0 / 0 without a bank; either pointer may be NULL. */
+int ewk_bank_info(ewk_engine* e, int32_t* n_words, int32_t* n_templates);
+/* Template `tmpl` (bank-wide index) of the bank; EWK_ENOTEMPLATE without a bank. */
+int ewk_bank_get(ewk_engine* e, int32_t tmpl, float* mean20, float* std20);
+/* Score segment i against the templates of word[i] (word NULL: word 0).  Host buffers.
+ * out_scores (NULL or [n_seg][stride], stride >= the bank's largest word):
+ * out_scores[i * stride + j] is the score against template word_first[word[i]] + j, NaN at
+ * and past the word's size.  flags: EWK_SCORE_F32_CANDIDATES.  EWK_ENOTEMPLATE without a
+ * bank; EWK_EINVAL for a word index outside [0, n_words). */
+int ewk_score_segments_bank(ewk_engine* e, const float* pcm, int64_t n_pcm, const int64_t* offsets,
+                            const int32_t* lengths, int32_t n_seg, const int32_t* word,
+                            ewk_bank_result* out, double* out_scores, int32_t stride, int32_t flags);
+/* Device-resident variant: every pointer is device memory, `stream` a hipStream_t (NULL = the
+ * engine's stream).  Not fully asynchronous: after the float32 pass the count of segments
+ * that need the fp64 statistics is read back (a 4-byte copy and one synchronisation of
+ * `stream`); the fp64 pass, when there is one, is then enqueued and the call returns without
+ * waiting for it.  A word[i] outside [0, n_words) cannot be checked from the host: that
+ * segment gets best_tmpl = -1, a NaN best_score, no hit, and NaN in its out_scores row. */
+int ewk_score_segments_bank_device(ewk_engine* e, const float* d_pcm, const int64_t* d_offsets,
+                                   const int32_t* d_lengths, int32_t n_seg, const int32_t* d_word,
+                                   ewk_bank_result* d_out, double* d_out_scores, int32_t stride,
+                                   int32_t flags, void* stream);
+
 /* ---- level 1 + 2: the streaming gate (SoundBuffer + _detect_word) ------------ */
 
 /* One tick for every stream: SoundBuffer._add_sound_to_buffer with a `block`
