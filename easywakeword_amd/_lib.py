@@ -25,6 +25,8 @@ EWK_ENODEV = -5
 EWK_EOVERWRITTEN = -6
 EWK_EV_SKIPPED = 1
 EWK_EV_RESCORED = 2
+EWK_EV_BANK = 4          # scored against the stream bank (StreamEngine.set_stream_bank)
+EWK_EV_BEST_SHIFT = 8    # ... its best template within the word: bits 8..13 of flags
 # |MFCC mean vector| below which a segment's score comes from the fp64 re-score (the scorer's
 # kTinyMean, csrc/ewk_mfcc.hip; tests/test_rescore_criteria.py keeps the two equal)
 RESCORE_TINY_MEAN = 32.0
@@ -56,6 +58,7 @@ EXPORTS = [
     "ewk_decode_pcm16", "ewk_poll_lagged", "ewk_runtime_info", "ewk_reenter", "ewk_compact_positives",
     "ewk_bank_set", "ewk_bank_from_pcm", "ewk_bank_clear", "ewk_bank_info", "ewk_bank_get",
     "ewk_score_segments_bank", "ewk_score_segments_bank_device",
+    "ewk_stream_bank_enable", "ewk_stream_bank_disable",
 ]
 
 
@@ -187,6 +190,8 @@ def load():
                                                   C.POINTER(EwkBankResult), _dp, C.c_int32, C.c_int32]),
             "ewk_score_segments_bank_device": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_int32,
                                                          C.c_int32, _P]),
+            "ewk_stream_bank_enable": (C.c_int, [_P, _i32p]),
+            "ewk_stream_bank_disable": (C.c_int, [_P]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)
@@ -212,6 +217,12 @@ def check(rc: int) -> None:
     if rc == EWK_ENOMEM:
         raise MemoryError(msg)
     raise RuntimeError(f"ewk error {rc}: {msg}")
+
+
+def event_best_template(flags):
+    """The best template's index inside its word (include/ewk.h, EWK_EV_BEST) of an event scored
+    against the stream bank (EWK_EV_BANK, non-NaN score); works on an int or an array of flags."""
+    return (flags >> EWK_EV_BEST_SHIFT) & 63
 
 
 def default_config(**overrides) -> EwkConfig:

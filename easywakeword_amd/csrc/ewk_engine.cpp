@@ -119,6 +119,16 @@ struct ewk_engine {
     DevBuf<int32_t> bk_word;                  // host-call staging
     DevBuf<ewk_bank_result> bk_out;
     DevBuf<double> bk_scores;
+    // stream bank (ewk_stream_bank_enable): gated events are scored against the bank.  Per event
+    // slot (one set for both event banks: scoring passes are serialised on their stream) the
+    // float32 statistics and theta_s of the ring scorer, the fp64 statistics of the re-score, and
+    // the list of the events a pass re-scores (BankEvArgs::ev_list); allocated at the first enable.
+    bool sbank_on = false;
+    bool sbank_words = false;                 // sb_word holds a word per stream (else: word 0)
+    DevBuf<int32_t> sb_word;                  // [n_streams]
+    DevBuf<float> sb_mean, sb_std, sb_theta;  // [ev_cap][20], [ev_cap][20], [ev_cap]
+    DevBuf<double> sb_mean64, sb_std64;       // [ev_cap][20]
+    DevBuf<int32_t> sb_list;                  // [kEvListHdr + ev_cap]
 
     // streaming
     void* d_ring = nullptr;         // float32 or int16 samples (cfg.ring_format)
@@ -348,6 +358,13 @@ void ewk_destroy(ewk_engine* e) {
     e->bk_word.release();
     e->bk_out.release();
     e->bk_scores.release();
+    e->sb_word.release();
+    e->sb_mean.release();
+    e->sb_std.release();
+    e->sb_theta.release();
+    e->sb_mean64.release();
+    e->sb_std64.release();
+    e->sb_list.release();
     e->push_stage.release();
     (void)hipFree(e->d_ring);
     (void)hipFree(e->d_brms);
@@ -761,6 +778,7 @@ int ewk_template_from_pcm(ewk_engine* e, const float* pcm, int64_t n) {
 // ---------------------------------------------------------------- template bank
 static_assert(sizeof(ewk_bank_result) == 24, "ewk_bank_result is 24 bytes (include/ewk.h)");
 static const char* kNoBank = "No reference word set. Call set_bank() first.";
+static const char* kStreamBankOn = "disable the stream bank first";
 
 static int check_bank_layout(int32_t n_words, const int32_t* word_first) {
     if (n_words < 1) return fail(EWK_EINVAL, "a bank needs at least one word");
@@ -782,6 +800,7 @@ static int check_bank_layout(int32_t n_words, const int32_t* word_first) {
 int ewk_bank_set(ewk_engine* e, int32_t n_words, const int32_t* word_first, const float* mean, const float* stdv,
                  const double* thresholds) {
     if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (e->sbank_on) return fail(EWK_EINVAL, kStreamBankOn);
     int rc = check_bank_layout(n_words, word_first);
     if (rc) return rc;
     if (!mean || !stdv) return fail(EWK_EINVAL, "NULL argument");
@@ -835,6 +854,7 @@ int ewk_bank_set(ewk_engine* e, int32_t n_words, const int32_t* word_first, cons
 int ewk_bank_from_pcm(ewk_engine* e, int32_t n_words, const int32_t* word_first, const float* pcm, int64_t n_pcm,
                       const int64_t* offsets, const int32_t* lengths, const double* thresholds) {
     if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (e->sbank_on) return fail(EWK_EINVAL, kStreamBankOn);
     int rc = check_bank_layout(n_words, word_first);
     if (rc) return rc;
     if (!pcm || !offsets || !lengths || n_pcm < 0) return fail(EWK_EINVAL, "NULL argument");
@@ -853,6 +873,7 @@ int ewk_bank_from_pcm(ewk_engine* e, int32_t n_words, const int32_t* word_first,
 
 int ewk_bank_clear(ewk_engine* e) {
     if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (e->sbank_on) return fail(EWK_EINVAL, kStreamBankOn);
     e->bank_first.clear();
     e->bank_mean.clear();
     e->bank_std.clear();
@@ -878,6 +899,31 @@ int ewk_bank_get(ewk_engine* e, int32_t tmpl, float* mean20, float* std20) {
     return EWK_OK;
 }
 
+// A bank set with NULL thresholds follows the engine's threshold as it stands at each scoring
+// call: refresh the device copy on `s` when it moved (the only case that waits for `s`).
+static int bank_follow_threshold(ewk_engine* e, hipStream_t s) {
+    if (!e->bank_thr_follow || e->bank_thr[0] == e->cfg.similarity_threshold) return EWK_OK;
+    std::fill(e->bank_thr.begin(), e->bank_thr.end(), e->cfg.similarity_threshold);
+    HIP_TRY(hipMemcpyAsync(e->d_bank_thr.p, e->bank_thr.data(), e->bank_thr.size() * sizeof(double),
+                           hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));   // (the copy reads bank_thr)
+    return EWK_OK;
+}
+
+// What every bank pass takes from the engine's bank.
+static BankArgs bank_args(ewk_engine* e) {
+    BankArgs b;
+    memset(&b, 0, sizeof(b));
+    b.bank = e->d_bank.p;
+    b.word_first = e->d_bank_first.p;
+    b.thresholds = e->d_bank_thr.p;
+    b.n_words = (int32_t)e->bank_first.size() - 1;
+    b.max_word = e->bank_max_word;
+    b.rescore_margin = e->cfg.rescore_margin;
+    b.crit = rescore_criteria();
+    return b;
+}
+
 // The three passes on `s` (device pointers): float32 statistics, bank scores + fp64 list,
 // then -- after reading the list count back -- the fp64 statistics of the listed segments and
 // their scores again.
@@ -892,11 +938,9 @@ static int bank_score(ewk_engine* e, const float* d_pcm, const int64_t* d_off, c
     HIP_TRY(e->bk_off.reserve(n));
     HIP_TRY(e->bk_len.reserve(n));
     HIP_TRY(join_scoring(e, s));
-    if (e->bank_thr_follow && e->bank_thr[0] != e->cfg.similarity_threshold) {
-        std::fill(e->bank_thr.begin(), e->bank_thr.end(), e->cfg.similarity_threshold);
-        HIP_TRY(hipMemcpyAsync(e->d_bank_thr.p, e->bank_thr.data(), e->bank_thr.size() * sizeof(double),
-                               hipMemcpyHostToDevice, s));
-        HIP_TRY(hipStreamSynchronize(s));   // (the copy reads bank_thr)
+    {
+        int rc = bank_follow_threshold(e, s);
+        if (rc) return rc;
     }
     ScoreArgs a = base_args(e);
     a.has_template = 0;   // pass 1: statistics only, nothing listed
@@ -911,13 +955,7 @@ static int bank_score(ewk_engine* e, const float* d_pcm, const int64_t* d_off, c
         ProfScope ps(e, 0, s);
         HIP_TRY(launch_score_f32(e->d_tab, a, 0, s));
     }
-    BankArgs b;
-    memset(&b, 0, sizeof(b));
-    b.bank = e->d_bank.p;
-    b.word_first = e->d_bank_first.p;
-    b.thresholds = e->d_bank_thr.p;
-    b.n_words = (int32_t)e->bank_first.size() - 1;
-    b.max_word = e->bank_max_word;
+    BankArgs b = bank_args(e);
     b.mean = e->mean.p;
     b.stdv = e->stdv.p;
     b.offsets = d_off;
@@ -928,8 +966,6 @@ static int bank_score(ewk_engine* e, const float* d_pcm, const int64_t* d_off, c
     b.out_scores = d_scores;
     b.stride = stride;
     b.cand_f32 = (flags & EWK_SCORE_F32_CANDIDATES) ? 1 : 0;
-    b.rescore_margin = e->cfg.rescore_margin;
-    b.crit = rescore_criteria();
     b.list_cnt = e->bk_cnt.p;
     b.list_seg = e->bk_seg.p;
     b.list_off = e->bk_off.p;
@@ -1050,6 +1086,8 @@ int ewk_reset_streams(ewk_engine* e) {
     }
     HIP_TRY(hipMemcpyAsync(e->d_st, st.data(), st.size() * sizeof(GateStream), hipMemcpyHostToDevice, s));
     HIP_TRY(hipMemsetAsync(e->d_work, 0, kWorkInts * sizeof(int32_t), s));
+    // (a stream bank stays enabled; its list of events to re-score starts empty)
+    if (e->sb_list.p) HIP_TRY(hipMemsetAsync(e->sb_list.p, 0, kEvListHdr * sizeof(int32_t), s));
     zero_event_state(e);
     HIP_TRY(hipStreamSynchronize(s));
     e->tick = 0;
@@ -1059,7 +1097,10 @@ int ewk_reset_streams(ewk_engine* e) {
 // Score the events queued since the last scoring pass (ring mode), then advance the watermark.
 // Score the current bank's events [ev_base, *n_events) on stream ss; n_events is the
 // live counter (same stream as the gate) or a snapshot of it taken after the gate.
+static int score_pending_bank(ewk_engine* e, hipStream_t ss, const int32_t* n_events);
+
 static int score_pending(ewk_engine* e, hipStream_t ss, const int32_t* n_events) {
+    if (e->sbank_on) return score_pending_bank(e, ss, n_events);   // (needs no single template)
     if (!e->has_tmpl) return EWK_OK;   // events keep NaN scores until a template exists
     ScoreArgs a = base_args(e);
     a.pcm = e->ring_f32();
@@ -1087,6 +1128,108 @@ static int score_pending(ewk_engine* e, hipStream_t ss, const int32_t* n_events)
         ProfScope ps(e, 1, ss);
         HIP_TRY(launch_rescore_ring(a, ss));
     }
+    return EWK_OK;
+}
+
+// Workgroups of the stream bank's event passes: the waves stride over the pending events, so
+// the grid follows the engine's size (an empty tick only pays for reading the counters).
+static int32_t stream_bank_grid(const ewk_engine* e) {
+    return std::min(1024, std::max(8, (e->n_streams + 255) / 256));
+}
+
+// The same pass with the stream bank enabled, all on ss, every hand-off a kernel boundary:
+//   1 the ring scorer without a template: float32 statistics and theta_s by event slot
+//   2 k_bank_events<float>: every pending event against its stream's word; lists the events the
+//     float32 statistics cannot decide (re-score slots + sb_list)
+//   3 the re-score launch: fp64 statistics of the listed events; ends the tick (counters,
+//     watermark) without the poll mirror -- pass 4 still changes events
+//   4 k_bank_events<double>: the listed events again from the fp64 statistics
+// push_impl writes the poll mirror behind the push's last pass.
+static int score_pending_bank(ewk_engine* e, hipStream_t ss, const int32_t* n_events) {
+    {
+        int rc = bank_follow_threshold(e, ss);
+        if (rc) return rc;
+    }
+    ScoreArgs a = base_args(e);
+    a.has_template = 0;
+    a.pcm = e->ring_f32();
+    a.pcm16 = e->ring_i16();
+    a.ring_len = e->sring_len;
+    a.events = e->ev_bank(e->bank);
+    a.n_events = n_events;
+    a.ev_base = e->evc_bank(e->bank) + 2;
+    a.ev_base0 = e->ev_base0[e->bank];
+    a.n_seg = e->ev_cap;
+    a.work = e->d_work + 1;
+    a.rs_ctl = e->d_work + 16;
+    a.rs_slots = e->rs_slots.p;
+    a.adv_ev_base = e->evc_bank(e->bank) + 2;
+    a.out_mean = e->sb_mean.p;
+    a.out_std = e->sb_std.p;
+    a.out_theta = e->sb_theta.p;
+    a.out_mean64 = e->sb_mean64.p;
+    a.out_std64 = e->sb_std64.p;
+    a.evc = e->evc_bank(e->bank);
+    BankArgs b = bank_args(e);
+    BankEvArgs x;
+    x.stream_word = e->sbank_words ? e->sb_word.p : nullptr;
+    x.ev_list = e->sb_list.p;
+    x.grid = stream_bank_grid(e);
+    {
+        ProfScope ps(e, 0, ss);
+        HIP_TRY(launch_score_f32(e->d_tab, a, e->n_streams >= kRingWaveStreams ? 2 : 1, ss));
+    }
+    b.mean = e->sb_mean.p;
+    b.stdv = e->sb_std.p;
+    HIP_TRY(launch_bank_events(b, a, x, ss));
+    {
+        ProfScope ps(e, 1, ss);
+        HIP_TRY(launch_rescore_ring(a, ss));
+    }
+    b.mean = e->sb_mean64.p;
+    b.stdv = e->sb_std64.p;
+    HIP_TRY(launch_bank_events_rescore(b, a, x, ss));
+    return EWK_OK;
+}
+
+int ewk_stream_bank_enable(ewk_engine* e, const int32_t* stream_word) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (e->n_streams <= 0) return fail(EWK_EINVAL, "engine has no streams");
+    if (e->bank_first.empty()) return fail(EWK_ENOTEMPLATE, kNoBank);
+    const int32_t n_words = (int32_t)e->bank_first.size() - 1;
+    if (stream_word)
+        for (int32_t s = 0; s < e->n_streams; ++s)
+            if (stream_word[s] < 0 || stream_word[s] >= n_words)
+                return fail(EWK_EINVAL, "word index " + std::to_string(stream_word[s]) + " of stream " +
+                                            std::to_string(s) + " is outside [0, " + std::to_string(n_words) + ")");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));    // the pushes so far keep their scoring
+    HIP_TRY(hipStreamSynchronize(e->sstream));
+    const size_t cap = (size_t)e->ev_cap;
+    const bool fresh = e->sb_list.p == nullptr;
+    HIP_TRY(e->sb_mean.reserve(cap * NMFCC));
+    HIP_TRY(e->sb_std.reserve(cap * NMFCC));
+    HIP_TRY(e->sb_theta.reserve(cap));
+    HIP_TRY(e->sb_mean64.reserve(cap * NMFCC));
+    HIP_TRY(e->sb_std64.reserve(cap * NMFCC));
+    HIP_TRY(e->sb_list.reserve(kEvListHdr + cap));
+    if (fresh) HIP_TRY(hipMemset(e->sb_list.p, 0, kEvListHdr * sizeof(int32_t)));
+    if (stream_word) {
+        HIP_TRY(e->sb_word.reserve((size_t)e->n_streams));
+        HIP_TRY(hipMemcpy(e->sb_word.p, stream_word, (size_t)e->n_streams * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    e->sbank_words = stream_word != nullptr;
+    e->sbank_on = true;
+    return EWK_OK;
+}
+
+int ewk_stream_bank_disable(ewk_engine* e) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (!e->sbank_on) return EWK_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipStreamSynchronize(e->sstream));
+    e->sbank_on = false;
     return EWK_OK;
 }
 
@@ -1196,9 +1339,10 @@ static int push_impl(ewk_engine* e, const void* pcm_any, int64_t stride, int64_t
         }
         e->push_seq += 1;
     }
-    // the poll mirror of this bank: written by the last scoring pass's tick end, or (no template
-    // yet: no scoring pass) by k_bank_mirror behind the gate
-    if (!e->has_tmpl) {
+    // the poll mirror of this bank: written by the last scoring pass's tick end, or by
+    // k_bank_mirror: behind the gate (no template yet: no scoring pass), or behind the stream
+    // bank's last pass (its fp64 pass changes events after the tick end)
+    if (e->sbank_on || !e->has_tmpl) {
         hipStream_t ms = e->overlap ? e->sstream : s;
         HIP_TRY(ensure_poll_region(e));
         HIP_TRY(launch_bank_mirror(e->evc_bank(e->bank), e->ev_bank(e->bank), e->ev_base0[e->bank], e->ev_cap,

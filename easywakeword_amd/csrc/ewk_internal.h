@@ -116,8 +116,9 @@ struct ScoreArgs {
     int32_t cand_f32;         // candidate dtype of the reference path: 1 float32, 0 float64
     const float* tmpl;        // [40] template mean[20], std[20]
     float uu_m32, uu_s32;     // template self-dots as numpy computes them (float32 sdot)
-    float* out_mean;
+    float* out_mean;          // linear mode by segment; ring modes (nullptr: none) by event slot
     float* out_std;
+    float* out_theta;         // ring modes (nullptr: none): the pass's theta_s by event slot
     double* out_score;
     uint8_t* out_match;
     double threshold;
@@ -203,6 +204,27 @@ struct BankArgs {
 };
 hipError_t launch_bank_score(const BankArgs& a, hipStream_t s);     // (zeroes *list_cnt first)
 hipError_t launch_bank_rescore(const BankArgs& a, hipStream_t s);
+
+// Stream bank (ewk_bank.hip, k_bank_events): the pending events of a ring-mode scoring pass
+// against the templates of their streams' words, with k_bank's code.  Between the ring scorer
+// without a template (statistics by event slot: ScoreArgs::out_mean / out_std / out_theta) and
+// launch_rescore_ring, the float32 pass scores every event of the pending window -- read
+// device-side as the ring scorer reads it -- and lists those it cannot decide: into the
+// re-score slots (rs_list) and, as a count plus event slots, into ev_list.  After
+// launch_rescore_ring (fp64 statistics by event slot: out_mean64 / out_std64) the fp64 pass
+// scores the events of ev_list again and its last workgroup out zeroes the count.
+// BankArgs: bank, word_first, thresholds, n_words, max_word, rescore_margin, crit, and mean /
+// stdv = the statistics by event slot (float32 or float64); the rest is unused.
+// ScoreArgs: events, n_events, ev_base, ev_base0, n_seg (capacity), out_theta and the re-score
+// list (rs_ctl, rs_slots, rs_serial, rs_cap, rs_parts, rs_part_cap).
+constexpr int kEvListHdr = 4;   // ints before ev_list's slots: [0] count, [1] workgroups out
+struct BankEvArgs {
+    const int32_t* stream_word;   // [n_streams]; nullptr: word 0
+    int32_t* ev_list;             // [kEvListHdr + capacity]
+    int32_t grid;                 // workgroups (fixed per engine: the waves stride over the events)
+};
+hipError_t launch_bank_events(const BankArgs& b, const ScoreArgs& a, const BankEvArgs& x, hipStream_t s);
+hipError_t launch_bank_events_rescore(const BankArgs& b, const ScoreArgs& a, const BankEvArgs& x, hipStream_t s);
 
 constexpr int kScoreGridMax = 256;   // one resident workgroup wave of the grid
 constexpr int kScoreGridRing = 256;                     // ring-mode grid (device-side event count)

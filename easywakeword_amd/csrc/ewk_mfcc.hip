@@ -52,6 +52,7 @@
 #include "ewk_score.h"  // the score arithmetic and listing constants shared with ewk_bank.hip
 #include "ewk_db64.h"  // (the fp64 re-score's 10 log10, ewk_rescore.h)
 #include "ewk_topdb_shift.h"
+#include "ewk_rs_list.h"  // (listing for the fp64 re-score, shared with ewk_bank.hip)
 
 // s_setprio 1 over the frame-pass LDS phases (window, transposes, mel): -0.4 %
 #define EWK_SETPRIO(v) __builtin_amdgcn_s_setprio(v)
@@ -1728,6 +1729,18 @@ __device__ __forceinline__ void score_epilogue(const ScoreArgs& a, float cmf, fl
 }
 
 
+// Ring modes, statistics for the stream bank (k_bank_events, ewk_bank.hip): the event's float32
+// mean / std and the pass's theta_s by event slot (nullptr: none; one wave, lane k < 20:
+// coefficient k).
+__device__ __forceinline__ void ring_stats_store(const ScoreArgs& a, int seg, int lane, float cmf, float csf,
+                                                 float theta_s) {
+    if (lane < NMFCC) {
+        if (a.out_mean) a.out_mean[(int64_t)seg * NMFCC + lane] = cmf;
+        if (a.out_std) a.out_std[(int64_t)seg * NMFCC + lane] = csf;
+    }
+    if (lane == 0 && a.out_theta) a.out_theta[seg] = theta_s;
+}
+
 // MODE 0: linear batch; 1: ring events, one segment per workgroup (cooperative); 2: ring
 // events, one segment per wave from the work counter.  S16: int16 rings (EWK_RING_I16).
 template <int MODE, int S16>
@@ -1854,6 +1867,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_score_f32(const Tables* __res
                 if (lane == 0) g_coop_ev[dkey][wave] = make_int4(ev.stream, (int)ev.ring_start, ev.length, (int)ev.tick);
 #endif
                 segment_stats_coop(v, smem, scr, tile, spec, wave, lane, lo, misc0, theta_s EWK_COOP_KEY_ARG(dkey));
+                if (wave == 0) ring_stats_store(a, seg, lane, act ? misc0[lane] : 0.0f, act ? misc0[20 + lane] : 0.0f, theta_s);
                 if (wave == 0 && (a.has_template || a.list_all))
                     score_epilogue<RING>(a, act ? misc0[lane] : 0.0f, act ? misc0[20 + lane] : 0.0f, tmf, tsf, lane,
                                          seg, v.len, theta_s);
@@ -1903,6 +1917,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void k_score_f32(const Tables* __res
             if (a.out_mean) a.out_mean[(int64_t)seg * NMFCC + lane] = cmf;
             if (a.out_std) a.out_std[(int64_t)seg * NMFCC + lane] = csf;
         }
+        if (RING) ring_stats_store(a, seg, lane, cmf, csf, theta_s);
 #ifndef EWK_SKIP_EPI
         if (a.has_template || a.list_all) score_epilogue<RING>(a, cmf, csf, tmf, tsf, lane, seg, v.len, theta_s);
 #else

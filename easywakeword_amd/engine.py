@@ -445,6 +445,26 @@ class StreamEngine(Engine):
     def reset(self) -> None:
         check(self._lib.ewk_reset_streams(self._h))
 
+    # -- stream bank: gated events against many references, per stream ------------
+    def set_stream_bank(self, stream_word=None) -> None:
+        """From the next push on, every gated event of stream s is scored on the device against
+        the templates of word stream_word[s] of this engine's bank (set_bank / bank_from_pcm;
+        None: word 0 for every stream) instead of the single template.  Events then carry the
+        best score, the decision at the word's threshold and _lib.EWK_EV_BANK with the best
+        template in their flags (_lib.event_best_template).  set_bank / bank_from_pcm /
+        clear_bank raise ValueError until clear_stream_bank()."""
+        wp = None
+        if stream_word is not None:
+            stream_word = np.ascontiguousarray(stream_word, dtype=np.int32).reshape(-1)
+            if stream_word.size != self.n_streams:
+                raise ValueError(f"{stream_word.size} word indices for {self.n_streams} streams")
+            wp = _lib.i32ptr(stream_word)
+        check(self._lib.ewk_stream_bank_enable(self._h, wp))
+
+    def clear_stream_bank(self) -> None:
+        """Back to the single template (no-op when the stream bank is off)."""
+        check(self._lib.ewk_stream_bank_disable(self._h))
+
     def reenter(self, stream: int = -1, reentry_timeout: float = 0.0) -> None:
         """A new _detect_word call (wakeword.py:1048-1057) on `stream` (-1 = all) and the
         re-entry timeout for later pushes (0 = continuous, > 0 = start() mode)."""

@@ -29,6 +29,7 @@ from typing import Callable, Dict, Optional, Tuple, Union
 
 import numpy as np
 
+from . import _lib
 from . import audio as _audio
 from .engine import Engine, StreamEngine
 
@@ -305,6 +306,7 @@ class WakeWord:
         self.textword = textword.lower().strip()
         # several recordings of the word: the first is the stream engine's template (and the
         # one the speech durations are analysed from); events are decided against all of them
+        # (the stream engine's bank, on the device)
         self._wavwords = [wavword] if isinstance(wavword, (str, bytes)) or hasattr(wavword, "__fspath__") \
             else list(wavword)
         if not self._wavwords:
@@ -465,8 +467,15 @@ class WakeWord:
                 self._matcher.load_references_from_files(self._wavwords, self.textword)
             else:
                 self._matcher.load_reference_from_file(self.wavword, self.textword)
-            self._sound_buffer.engine.set_template(self._matcher.reference_mfcc_mean,
-                                                   self._matcher.reference_mfcc_std)
+            eng = self._sound_buffer.engine
+            eng.set_template(self._matcher.reference_mfcc_mean, self._matcher.reference_mfcc_std)
+            if len(self._wavwords) > 1:
+                # every reference into the stream engine's bank (one word, the engine's
+                # threshold): gated events are decided against all of them on the device
+                refs = [self._matcher.engine.bank_template(k) for k in range(len(self._wavwords))]
+                eng.clear_stream_bank()
+                eng.set_bank([refs])
+                eng.set_stream_bank()
 
     def _wait_for_buffer(self) -> None:
         while not self._sound_buffer.is_buffer_full():
@@ -499,18 +508,15 @@ class WakeWord:
         for ev in events:
             if ev["flags"] & 1:   # too long: skipped (wakeword.py:1113-1118)
                 continue
-            if len(self._wavwords) > 1:
-                # the stream scored reference 0 only: decide against every reference on the
-                # matcher's scorer (float64 candidates, as the stream's segments are)
-                audio = self._sound_buffer.engine.read_segment(0, int(ev["ring_start"]), int(ev["length"]))
-                res = self._matcher.score_bank([audio.astype(np.float64)], self.similarity_threshold)
-                self._log(f"MFCC similarity: {res['best_score'][0]:.1f}% (reference {res['best_tmpl'][0]})")
-                if not res["match"][0]:
-                    continue
+            if ev["flags"] & _lib.EWK_EV_BANK:
+                # several references: the stream engine scored the event against all of them
+                # (its stream bank) in the same push; the flags name the best one
+                self._log(f"MFCC similarity: {ev['score']:.1f}% "
+                          f"(reference {_lib.event_best_template(int(ev['flags']))})")
             else:
                 self._log(f"MFCC similarity: {ev['score']:.1f}%")
-                if not ev["match"]:
-                    continue
+            if not ev["match"]:
+                continue
             if self._confirm is None:
                 return self.textword
             audio = self._sound_buffer.engine.read_segment(0, int(ev["ring_start"]), int(ev["length"]))

@@ -46,6 +46,13 @@ extern "C" {
                                  rescore_margin, or the segment is very short (<= 16 frames), nearly
                                  stationary (|std| < 20) or has a vanishing MFCC mean (|mean| < 32,
                                  unless its similarity is negative beyond the fp32 error: NaN either way) */
+#define EWK_EV_BANK 4         /* scored against the stream bank (ewk_stream_bank_enable): score = best
+                                 score over the templates of the stream's word ignoring NaN (NaN when
+                                 all are), match = best >= the word's threshold */
+#define EWK_EV_BEST_SHIFT 8   /* with EWK_EV_BANK and a non-NaN score: bits 8..13 of flags hold the best
+                                 template's index inside its word (lowest on ties), as
+                                 ewk_bank_result.best_tmpl minus word_first[w] */
+#define EWK_EV_BEST(flags) (((flags) >> EWK_EV_BEST_SHIFT) & 63)
 
 /* ewk_score_segments* flags */
 #define EWK_SCORE_REQUIRE_TEMPLATE 1   /* EWK_ENOTEMPLATE when no template (calculate_similarity) */
@@ -269,8 +276,25 @@ int ewk_reenter(ewk_engine* e, int32_t stream, double reentry_timeout);
 int ewk_read_last(ewk_engine* e, int32_t stream, int64_t n_samples, float* out, int64_t* n_out);
 /* Copy the samples of a queued/polled event (ring must not have wrapped over it). */
 int ewk_read_segment(ewk_engine* e, int32_t stream, int64_t ring_start, int32_t length, float* out);
-/* Reset all stream state (ring, threshold, FSM, event queue). */
+/* Reset all stream state (ring, threshold, FSM, event queue).  A stream bank stays enabled. */
 int ewk_reset_streams(ewk_engine* e);
+
+/* ---- level 1 + 2 against many references: the stream bank ---------------------- */
+/* From the next push on, every gated event of stream s is scored against the templates of word
+ * stream_word[s] of the engine's bank (NULL: word 0 for every stream) instead of the single
+ * template, on the device and in the same push: the event carries the best score, the decision
+ * (per-word threshold, or the engine's as it stands at each push when the bank was set with
+ * NULL thresholds) and, in its flags, EWK_EV_BANK and the best template (EWK_EV_BEST).
+ * Candidates are float64, as on the whole ring path.  No single template is needed.  The
+ * per-template hit_mask and score row are not delivered per event: a caller who wants them
+ * reads the segment back (ewk_read_segment) and scores it with ewk_score_segments_bank.
+ * Host array [n_streams], copied.  EWK_ENOTEMPLATE without a bank, EWK_EINVAL for an engine
+ * without streams or an index outside [0, n_words).  Waits for the pushes so far.  While
+ * enabled, ewk_bank_set / ewk_bank_from_pcm / ewk_bank_clear return EWK_EINVAL ("disable the
+ * stream bank first").  The first call allocates the per-event buffers (488 bytes per event
+ * slot, 4 slots per stream), freed with the engine. */
+int ewk_stream_bank_enable(ewk_engine* e, const int32_t* stream_word);
+int ewk_stream_bank_disable(ewk_engine* e);   /* back to the single template; no-op when off */
 
 /* ---- either side of the path --------------------------------------- */
 /* Level-3 input: WakeWord._transcribe_audio's normalisation (wakeword.py:1019-1025)
