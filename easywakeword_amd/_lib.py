@@ -59,6 +59,7 @@ EXPORTS = [
     "ewk_bank_set", "ewk_bank_from_pcm", "ewk_bank_clear", "ewk_bank_info", "ewk_bank_get",
     "ewk_score_segments_bank", "ewk_score_segments_bank_device",
     "ewk_stream_bank_enable", "ewk_stream_bank_disable",
+    "ewk_resample_design", "ewk_resample", "ewk_set_input_rate", "ewk_input_rate_info",
 ]
 
 
@@ -192,6 +193,10 @@ def load():
                                                          C.c_int32, _P]),
             "ewk_stream_bank_enable": (C.c_int, [_P, _i32p]),
             "ewk_stream_bank_disable": (C.c_int, [_P]),
+            "ewk_resample_design": (C.c_int, [C.c_int32, C.c_int32, _dp, C.c_int32, _i32p, _i32p, _i32p]),
+            "ewk_resample": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, _i64p, C.c_int32]),
+            "ewk_set_input_rate": (C.c_int, [_P, C.c_int32]),
+            "ewk_input_rate_info": (C.c_int, [_P, _i32p, _i32p, _i32p]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)

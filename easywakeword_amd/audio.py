@@ -10,7 +10,9 @@ from this image), so resampled audio is close to, not bit-identical with, the
 reference's -- parity unpinned for non-16 kHz files.
 
 Sources replace the PortAudio input stream of SoundBuffer (wakeword.py:438-444):
-each yields float32 blocks of ``block`` samples, one per 0.1 s tick.
+each yields float32 blocks of ``block`` samples, one per 0.1 s tick -- or, for a source kept at
+its own sample rate (``rate=`` / ``native_rate=True`` / ``samplerate=``), the tick's samples at
+that rate, which the engine resamples on the device (StreamEngine.set_input_rate).
 """
 from __future__ import annotations
 
@@ -65,14 +67,27 @@ def write_wav(path: str, audio, sr: int = FREQUENCY) -> None:
         w.writeframes(q.tobytes())
 
 
+def input_block(block: int, rate: int) -> int:
+    """Samples per tick at `rate` Hz for a tick of `block` samples at 16 kHz (StreamEngine.input_block)."""
+    n = int(block) * int(rate)
+    if int(rate) <= 0 or n % FREQUENCY:
+        raise ValueError(f"a tick of {block} samples at {FREQUENCY} Hz is not a whole number of samples at {rate} Hz")
+    return n // FREQUENCY
+
+
 class ArraySource:
-    """Blocks from an in-memory float32 signal; zeros after the end (a silent mic)."""
+    """Blocks from an in-memory float32 signal; zeros after the end (a silent mic).
+    ``rate``: the signal's sample rate.  At another rate than 16 kHz every read yields the
+    tick's samples at that rate (``block * rate / 16000``; ``block`` stays the 16 kHz tick the
+    engine is built with) and the engine resamples them on the device."""
 
     realtime = False
 
-    def __init__(self, audio, block: int = 1600, loop: bool = False):
+    def __init__(self, audio, block: int = 1600, loop: bool = False, rate: int = FREQUENCY):
         self.audio = np.ascontiguousarray(np.asarray(audio, dtype=np.float32).reshape(-1))
         self.block = int(block)
+        self.rate = int(rate)
+        self.read_block = input_block(self.block, self.rate)
         self.loop = loop
         self.pos = 0
 
@@ -82,7 +97,7 @@ class ArraySource:
             yield b
 
     def read(self) -> np.ndarray:
-        n = self.block
+        n = self.read_block
         a = self.audio
         if self.loop and len(a):
             idx = (self.pos + np.arange(n)) % len(a)
@@ -107,25 +122,36 @@ class ArraySource:
 
 
 class WavSource(ArraySource):
-    def __init__(self, path: str, block: int = 1600, loop: bool = False):
-        super().__init__(load_wav(path), block=block, loop=loop)
+    """A WAV file: resampled to 16 kHz on the host when it is loaded, or, with
+    ``native_rate=True``, left at its own rate (``.rate``) and resampled on the device."""
+
+    def __init__(self, path: str, block: int = 1600, loop: bool = False, native_rate: bool = False):
+        if native_rate:
+            with wave.open(str(path), "rb") as w:
+                rate = w.getframerate()
+            super().__init__(load_wav(path, sr=rate), block=block, loop=loop, rate=rate)
+        else:
+            super().__init__(load_wav(path), block=block, loop=loop)
 
 
 class MicSource:
     """PortAudio microphone through ``sounddevice`` (only when installed); `device` is a
     PortAudio index -- easywakeword_amd.devices.AudioDeviceManager resolves names and
-    the reference's magic words."""
+    the reference's magic words.  ``samplerate``: open the device at its own rate (no
+    conversion inside PortAudio); the engine resamples the blocks on the device."""
 
     realtime = True
 
-    def __init__(self, device: Optional[int] = None, block: int = 1600):
+    def __init__(self, device: Optional[int] = None, block: int = 1600, samplerate: int = FREQUENCY):
         import queue
 
         import sounddevice as sd  # noqa: F401  (raises ImportError/OSError when absent)
         self._sd = sd
         self.block = int(block)
+        self.rate = int(samplerate)
+        self.read_block = input_block(self.block, self.rate)
         self.q: "queue.Queue[np.ndarray]" = queue.Queue()
-        self.stream = sd.InputStream(samplerate=FREQUENCY, channels=1, blocksize=self.block, device=device,
+        self.stream = sd.InputStream(samplerate=self.rate, channels=1, blocksize=self.read_block, device=device,
                                      callback=lambda indata, frames, t, status: self.q.put(
                                          np.array(indata, dtype=np.float32).reshape(-1).copy()))
 

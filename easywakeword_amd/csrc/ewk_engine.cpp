@@ -179,9 +179,24 @@ struct ewk_engine {
     int32_t gate_stage = 0;
     int32_t gate_val_len = 0;       // per-wave LDS doubles of the gate (tree values, sort scratch)
 
+    // input-rate resampler (ewk_resample.hip).  rs_in: the filter of ewk_set_input_rate, with the
+    // per-stream history ([n_streams][H] float32: the last H input samples) and the resampled
+    // ticks the gate reads ([n_streams][n_ticks * block], grown to the longest push so far);
+    // rs_one: the filter of the latest ewk_resample call.
+    struct RsFilter {
+        int32_t rate = 0, up = 1, down = 1, half = 0, J = 0, H = 0, threads = 0, span = 0;
+        int64_t c0 = 0;        // ResampleArgs::c0
+        DevBuf<double> taps;   // [J][up]
+    };
+    RsFilter rs_in, rs_one;
+    bool rs_on = false;
+    bool rs_fresh = true;   // no push since the history was cleared: the first `delay` outputs are zero
+    int32_t rs_in_block = 0, rs_delay = 0;
+    DevBuf<float> rs_hist, rs_out;
+
     // measurement: (start, stop) event pairs per kernel family
     bool prof = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[3];
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[4];
     std::vector<hipEvent_t> ev_pool;
 };
 
@@ -366,6 +381,10 @@ void ewk_destroy(ewk_engine* e) {
     e->sb_std64.release();
     e->sb_list.release();
     e->push_stage.release();
+    e->rs_in.taps.release();
+    e->rs_one.taps.release();
+    e->rs_hist.release();
+    e->rs_out.release();
     (void)hipFree(e->d_ring);
     (void)hipFree(e->d_brms);
     (void)hipFree(e->d_sorted);
@@ -1088,6 +1107,9 @@ int ewk_reset_streams(ewk_engine* e) {
     HIP_TRY(hipMemsetAsync(e->d_work, 0, kWorkInts * sizeof(int32_t), s));
     // (a stream bank stays enabled; its list of events to re-score starts empty)
     if (e->sb_list.p) HIP_TRY(hipMemsetAsync(e->sb_list.p, 0, kEvListHdr * sizeof(int32_t), s));
+    // (an input rate stays set; the resampler's history starts from silence again)
+    if (e->rs_hist.p) HIP_TRY(hipMemsetAsync(e->rs_hist.p, 0, e->rs_hist.cap * sizeof(float), s));
+    e->rs_fresh = true;
     zero_event_state(e);
     HIP_TRY(hipStreamSynchronize(s));
     e->tick = 0;
@@ -1243,7 +1265,10 @@ static int push_impl(ewk_engine* e, const void* pcm_any, int64_t stride, int64_t
         return fail(EWK_EINVAL, "an int16 ring (EWK_RING_I16) takes PCM16 pushes (ewk_push_pcm16)");
     const size_t es = pcm16 ? sizeof(int16_t) : sizeof(float);
     const unsigned char* pcm = static_cast<const unsigned char*>(pcm_any);
-    if (stride < e->cfg.block && e->n_streams > 1) return fail(EWK_EINVAL, "stride must be >= block");
+    // with an input rate set (ewk_set_input_rate) a tick is in_block samples at that rate
+    const int64_t in_block = e->rs_on ? e->rs_in_block : e->cfg.block;
+    if (stride < in_block && e->n_streams > 1)
+        return fail(EWK_EINVAL, e->rs_on ? "stride must be >= the input block (ewk_input_rate_info)" : "stride must be >= block");
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = e->stream;
     const void* src = pcm_any;
@@ -1251,7 +1276,7 @@ static int push_impl(ewk_engine* e, const void* pcm_any, int64_t stride, int64_t
     if (!(flags & EWK_PUSH_DEVICE)) {
         // Gather the caller's (pageable) blocks into pinned staging on the CPU, then
         // DMA asynchronously: the caller's buffer may die as soon as we return.
-        const size_t per_stream = (size_t)n_ticks * e->cfg.block;
+        const size_t per_stream = (size_t)n_ticks * in_block;
         const size_t total = per_stream * e->n_streams;
         if (e->h_stage_free) HIP_TRY(hipEventSynchronize(e->h_stage_free));   // previous DMA done
         if (total > e->h_stage_cap) {
@@ -1264,14 +1289,56 @@ static int push_impl(ewk_engine* e, const void* pcm_any, int64_t stride, int64_t
         if (!e->h_stage_free) HIP_TRY(hipEventCreateWithFlags(&e->h_stage_free, hipEventDisableTiming));
         for (int32_t st = 0; st < e->n_streams; ++st)
             for (int32_t t = 0; t < n_ticks; ++t)
-                memcpy(reinterpret_cast<unsigned char*>(e->h_stage) + ((size_t)st * per_stream + (size_t)t * e->cfg.block) * es,
-                       pcm + ((size_t)st * stride + (size_t)t * tick_stride) * es, e->cfg.block * es);
+                memcpy(reinterpret_cast<unsigned char*>(e->h_stage) + ((size_t)st * per_stream + (size_t)t * in_block) * es,
+                       pcm + ((size_t)st * stride + (size_t)t * tick_stride) * es, in_block * es);
         HIP_TRY(e->push_stage.reserve(total));
         HIP_TRY(hipMemcpyAsync(e->push_stage.p, e->h_stage, total * es, hipMemcpyHostToDevice, s));
         HIP_TRY(hipEventRecord(e->h_stage_free, s));
         src = e->push_stage.p;
         st_stride = (int64_t)per_stream;
+        tk_stride = in_block;
+    }
+    if (e->rs_on) {
+        // resample every tick of the push into rs_out, save the history for the next push, and
+        // hand the gate float32 16 kHz blocks
+        const ewk_engine::RsFilter& f = e->rs_in;
+        const size_t per_stream = (size_t)n_ticks * e->cfg.block;
+        if (per_stream * e->n_streams > e->rs_out.cap) {
+            HIP_TRY(hipStreamSynchronize(s));   // an earlier gate launch may still read the old buffer
+            HIP_TRY(e->rs_out.reserve(per_stream * e->n_streams));
+        }
+        ResampleArgs r;
+        memset(&r, 0, sizeof(r));
+        if (pcm16) r.in16 = static_cast<const int16_t*>(src);
+        else r.in = static_cast<const float*>(src);
+        r.stride = st_stride;
+        r.tick_stride = tk_stride;
+        r.in_block = in_block;
+        r.n_in = (int64_t)n_ticks * in_block;
+        r.hist = e->rs_hist.p;
+        r.out = e->rs_out.p;
+        r.out_stride = (int64_t)per_stream;
+        r.n_out = (int64_t)per_stream;
+        r.rows = e->n_streams;
+        r.taps = f.taps.p;
+        r.up = f.up;
+        r.down = f.down;
+        r.J = f.J;
+        r.H = f.H;
+        r.c0 = f.c0;
+        r.n_zero = e->rs_fresh ? e->rs_delay : 0;
+        r.threads = f.threads;
+        r.span = f.span;
+        {
+            ProfScope ps(e, 3, s);
+            HIP_TRY(launch_resample(r, s));
+            HIP_TRY(launch_resample_save(r, e->rs_hist.p, s));
+        }
+        e->rs_fresh = false;
+        src = e->rs_out.p;
+        st_stride = (int64_t)per_stream;
         tk_stride = e->cfg.block;
+        pcm16 = false;
     }
     // Segments must be scored before the ring overwrites them: <= ticks_per_launch ticks per gate launch.
     for (int32_t t0 = 0; t0 < n_ticks; t0 += e->ticks_per_launch) {
@@ -1518,6 +1585,158 @@ int ewk_decode_pcm16(ewk_engine* e, const int16_t* in, int64_t n, float* out, in
     return EWK_OK;
 }
 
+// ---------------------------------------------------------------- input-rate resampler
+int ewk_resample_design(int32_t in_rate, int32_t out_rate, double* taps, int32_t cap, int32_t* n_taps, int32_t* up,
+                        int32_t* down) {
+    if (in_rate <= 0 || out_rate <= 0) return fail(EWK_EINVAL, "sample rates must be positive");
+    int32_t u = 1, d = 1;
+    resample_ratio(in_rate, out_rate, &u, &d);
+    const int64_t n = 20 * (int64_t)std::max(u, d) + 1;
+    if (n > 0x7fffffffLL) return fail(EWK_EINVAL, "the filter of this rate pair has more than 2^31 taps");
+    if (up) *up = u;
+    if (down) *down = d;
+    if (n_taps) *n_taps = (int32_t)n;
+    if (!taps || cap < n) return fail(EWK_EINVAL, "taps holds fewer than " + std::to_string(n) + " values");
+    resample_taps(u, d, taps);
+    return EWK_OK;
+}
+
+// The filter in_rate -> cfg.sample_rate in the kernel's layout.  Waits for the engine's stream
+// before the taps of another rate replace those it may still read.
+static int rs_prepare(ewk_engine* e, ewk_engine::RsFilter& f, int32_t in_rate, bool streaming) {
+    if (f.rate == in_rate && f.taps.p) return EWK_OK;
+    int32_t up = 1, down = 1;
+    resample_ratio(in_rate, e->cfg.sample_rate, &up, &down);
+    const int64_t half = 10 * (int64_t)std::max(up, down), J = 2 * half / up + 1;
+    const int threads = resample_threads(up);
+    const int64_t span = threads ? resample_span(up, down, (int32_t)std::min<int64_t>(J, kRsMaxSpan), threads) : 0;
+    if (!threads || J + 1 > kRsMaxSpan || span > kRsMaxSpan)
+        return fail(EWK_EINVAL, "the filter " + std::to_string(in_rate) + " -> " + std::to_string(e->cfg.sample_rate) +
+                                    " Hz (up " + std::to_string(up) + ", down " + std::to_string(down) +
+                                    ") is over the size the resampler supports (up <= " + std::to_string(kRsMaxThreads) +
+                                    ", " + std::to_string(kRsMaxSpan) + " staged samples per workgroup)");
+    // streaming: the whole-signal resample delayed by ceil(half / down) samples
+    const int64_t c0 = streaming ? half - (half + down - 1) / down * down : half;
+    std::vector<double> h((size_t)(2 * half + 1)), tt((size_t)(J * up), 0.0);
+    resample_taps(up, down, h.data());
+    for (int64_t j = 0; j < J; ++j)
+        for (int64_t p = 0; p < up; ++p)
+            if (p + j * up <= 2 * half) tt[(size_t)(j * up + p)] = h[(size_t)(p + j * up)];
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    f.rate = 0;
+    HIP_TRY(f.taps.reserve(tt.size()));
+    HIP_TRY(hipMemcpy(f.taps.p, tt.data(), tt.size() * sizeof(double), hipMemcpyHostToDevice));
+    f.up = up;
+    f.down = down;
+    f.half = (int32_t)half;
+    f.c0 = c0;
+    f.J = (int32_t)J;
+    f.H = (int32_t)J + 1;
+    f.threads = threads;
+    f.span = (int32_t)span;
+    f.rate = in_rate;
+    return EWK_OK;
+}
+
+int ewk_resample(ewk_engine* e, const float* in, int64_t n_in, int32_t in_rate, float* out, int64_t cap,
+                 int64_t* n_out, int32_t flags) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (n_out) *n_out = 0;
+    if (in_rate <= 0) return fail(EWK_EINVAL, "sample rates must be positive");
+    if (n_in < 0 || n_in >= (1LL << 40)) return fail(EWK_EINVAL, "n_in must be in [0, 2^40)");
+    int32_t up = 1, down = 1;
+    resample_ratio(in_rate, e->cfg.sample_rate, &up, &down);
+    const int64_t no = (n_in * up + down - 1) / down;   // ceil(n_in * out / in)
+    if (n_out) *n_out = no;
+    if (cap < no) return fail(EWK_EINVAL, "out holds fewer than " + std::to_string(no) + " samples");
+    if (no == 0) return EWK_OK;
+    if (!in || !out) return fail(EWK_EINVAL, "NULL argument");
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    const bool in_dev = (flags & EWK_PCM_DEVICE) != 0, out_dev = (flags & EWK_OUT_DEVICE) != 0;
+    if (up == 1 && down == 1) {   // the engine's own rate: a copy (as resample_poly returns it)
+        HIP_TRY(hipMemcpyAsync(out, in, (size_t)n_in * sizeof(float), hipMemcpyDefault, s));
+        if (!in_dev || !out_dev) HIP_TRY(hipStreamSynchronize(s));
+        return EWK_OK;
+    }
+    int rc = rs_prepare(e, e->rs_one, in_rate, false);
+    if (rc) return rc;
+    const ewk_engine::RsFilter& f = e->rs_one;
+    TmpBuf<float> d_in, d_out;
+    if (!in_dev) {
+        HIP_TRY(d_in.reserve((size_t)n_in));
+        HIP_TRY(hipMemcpyAsync(d_in.p, in, (size_t)n_in * sizeof(float), hipMemcpyHostToDevice, s));
+    }
+    if (!out_dev) HIP_TRY(d_out.reserve((size_t)no));
+    ResampleArgs r;
+    memset(&r, 0, sizeof(r));
+    r.in = in_dev ? in : d_in.p;
+    r.in_block = n_in;
+    r.n_in = n_in;
+    r.out = out_dev ? out : d_out.p;
+    r.out_stride = no;
+    r.n_out = no;
+    r.rows = 1;
+    r.taps = f.taps.p;
+    r.up = f.up;
+    r.down = f.down;
+    r.J = f.J;
+    r.H = f.H;
+    r.c0 = f.c0;
+    r.threads = f.threads;
+    r.span = f.span;
+    {
+        ProfScope ps(e, 3, s);
+        HIP_TRY(launch_resample(r, s));
+    }
+    if (!out_dev) HIP_TRY(hipMemcpyAsync(out, d_out.p, (size_t)no * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (!in_dev || !out_dev) HIP_TRY(hipStreamSynchronize(s));   // (the staging buffers die on return)
+    return EWK_OK;
+}
+
+int ewk_set_input_rate(ewk_engine* e, int32_t in_rate) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (e->n_streams <= 0) return fail(EWK_EINVAL, "engine has no streams");
+    if (in_rate < 0) return fail(EWK_EINVAL, "in_rate must be >= 0");
+    HIP_TRY(hipSetDevice(e->device));
+    if (in_rate == 0 || in_rate == e->cfg.sample_rate) {
+        if (!e->rs_on) return EWK_OK;
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        e->rs_on = false;
+        return EWK_OK;
+    }
+    if (e->ring_es == sizeof(int16_t))
+        return fail(EWK_EINVAL, "an int16 ring (EWK_RING_I16) stores PCM16 as delivered: resampled samples are not int16");
+    int32_t up = 1, down = 1;
+    resample_ratio(in_rate, e->cfg.sample_rate, &up, &down);
+    if (((int64_t)e->cfg.block * down) % up)
+        return fail(EWK_EINVAL, "a tick of " + std::to_string(e->cfg.block) + " samples at " +
+                                    std::to_string(e->cfg.sample_rate) + " Hz is not a whole number of samples at " +
+                                    std::to_string(in_rate) + " Hz");
+    e->rs_on = false;   // (a failure below leaves the engine at its own rate)
+    int rc = rs_prepare(e, e->rs_in, in_rate, true);   // waits for the pushes so far when the rate changes
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const ewk_engine::RsFilter& f = e->rs_in;
+    const size_t nh = (size_t)e->n_streams * f.H;
+    if (nh > e->rs_hist.cap) HIP_TRY(e->rs_hist.reserve(nh));
+    HIP_TRY(hipMemset(e->rs_hist.p, 0, e->rs_hist.cap * sizeof(float)));
+    HIP_TRY(e->rs_out.reserve((size_t)e->n_streams * e->cfg.block));
+    e->rs_in_block = (int32_t)((int64_t)e->cfg.block * down / up);
+    e->rs_delay = (int32_t)((f.half + down - 1) / down);
+    e->rs_fresh = true;
+    e->rs_on = true;
+    return EWK_OK;
+}
+
+int ewk_input_rate_info(ewk_engine* e, int32_t* in_rate, int32_t* in_block, int32_t* delay) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (in_rate) *in_rate = e->rs_on ? e->rs_in.rate : e->cfg.sample_rate;
+    if (in_block) *in_block = e->rs_on ? e->rs_in_block : e->cfg.block;
+    if (delay) *delay = e->rs_on ? e->rs_delay : 0;
+    return EWK_OK;
+}
+
 // Event banks are drained in two steps so a failing poll consumes nothing:
 // peek_bank waits for the pushes into bank b (copy stream only, no wait on later
 // work) and fetches its counters with the first kPollChunk events; take_bank copies
@@ -1728,7 +1947,7 @@ int ewk_profile_enable(ewk_engine* e, int32_t on) {
 
 int ewk_profile_read(ewk_engine* e, int32_t kind, double* total_ms, int64_t* launches) {
     if (!e || !total_ms || !launches) return fail(EWK_EINVAL, "NULL argument");
-    if (kind < 0 || kind > 2) return fail(EWK_EINVAL, "kind must be 0, 1 or 2");
+    if (kind < 0 || kind > 3) return fail(EWK_EINVAL, "kind must be 0, 1, 2 or 3");
     HIP_TRY(hipSetDevice(e->device));
     double tot = 0.0;
     for (auto& p : e->ev[kind]) {

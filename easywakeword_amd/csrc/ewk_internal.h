@@ -246,6 +246,47 @@ struct L3Args {
 hipError_t launch_normalize(const L3Args& a, hipStream_t s);
 hipError_t launch_decode_pcm16(const int16_t* in, float* out, int64_t n, hipStream_t s);
 
+// Input-rate resampler (ewk_resample.hip): polyphase FIR in_rate -> cfg.sample_rate with the
+// filter of audio.resample (ewk_tables.cpp: up = out / gcd, down = in / gcd, half = 10 *
+// max(up, down), 2 * half + 1 taps).  Output n of a row is
+//   sum_j h[p + j * up] * X(i - j),  c = n * down + c0,  i = floor(c / up),  p = c - i * up,
+// j = J - 1 .. 0 (ascending input index, scipy's order) in float64, rounded once to float32.
+// X(i) is input sample i of the row: tick i / in_block, offset i % in_block of it; zero at and
+// past n_in; for i < 0 the row's history hist[H + i] (the H samples before sample 0), zero
+// without one.  c0 = half for the whole-signal resample, half - delay * down when streaming:
+// the stream is the whole-signal resample delayed by `delay` samples, and its first `delay`
+// samples (which would be the filter's ringing ahead of the signal) are zero.
+void resample_ratio(int32_t in_rate, int32_t out_rate, int32_t* up, int32_t* down);
+void resample_taps(int32_t up, int32_t down, double* h /* [20 * max(up, down) + 1] */);
+constexpr int kRsQ = 4;              // outputs per thread (they share a phase, so a tap load)
+constexpr int kRsMaxThreads = 1024;  // a workgroup covers whole periods of `up` outputs: up <= this
+constexpr int kRsMaxSpan = 12288;    // floats of input a workgroup stages in LDS (48 KB)
+struct ResampleArgs {
+    const float* in;          // float32 input, or
+    const int16_t* in16;      // int16 PCM (x / 32768)
+    int64_t stride;           // samples between rows (streams)
+    int64_t tick_stride;      // samples between the ticks of a row
+    int64_t in_block;         // samples per tick (one-shot: n_in)
+    int64_t n_in;             // input samples per row
+    const float* hist;        // nullptr or [rows][H]
+    float* out;               // [rows][out_stride]
+    int64_t out_stride;
+    int64_t n_out;            // outputs per row
+    int32_t rows;
+    const double* taps;       // [J][up]: taps[j * up + p] = h[p + j * up], zero past the filter
+    int32_t up, down, J, H;
+    int64_t c0;
+    int64_t n_zero;           // outputs n < n_zero are zero (a stream's first `delay` samples)
+    int32_t threads;          // resample_threads(up)
+    int32_t span;             // resample_span(up, down, J, threads) <= kRsMaxSpan
+};
+int resample_threads(int32_t up);   // workgroup size: a multiple of up (0: up > kRsMaxThreads)
+int64_t resample_span(int32_t up, int32_t down, int32_t J, int32_t threads);
+hipError_t launch_resample(const ResampleArgs& a, hipStream_t s);
+// hist[r][k] = X(n_in - H + k): the tail of a push, saved once every workgroup of launch_resample
+// has read the old one (stream order)
+hipError_t launch_resample_save(const ResampleArgs& a, float* hist, hipStream_t s);
+
 // ewk_gather.hip: positives compaction (scratch: 2 * compact_blocks(n) int32)
 int compact_blocks(int32_t n);
 hipError_t launch_compact_positives(const double* score, const uint8_t* match, int32_t n, int64_t first_id,

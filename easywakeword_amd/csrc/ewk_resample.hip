@@ -1,0 +1,118 @@
+// ewk_resample.hip -- input-rate resampler: polyphase FIR from a source's own sample rate to
+// the engine's 16 kHz, for whole signals (ewk_resample) and for the streaming push path
+// (ewk_set_input_rate), float32 or int16 PCM input.  The arithmetic is ResampleArgs'
+// (ewk_internal.h): only the taps of an output's phase are touched, J per output.
+//
+// One workgroup computes kRsQ * S consecutive outputs of one row, S = blockDim.x a multiple of
+// `up`: thread t owns outputs t, t + S, .. of the tile, which share a phase, so each tap is
+// loaded once for kRsQ outputs.  The tile's input span, history included, is staged in LDS
+// once with coalesced loads (int16 decoded on the way); outputs are stored coalesced.  The tap
+// table is [J][up] (phase-minor) and read through L1/L2: with up = 1 (48, 32, 96 kHz) a tap
+// load is one address for the whole wave.
+#include "ewk_internal.h"
+
+namespace ewk {
+
+// X(i) of a row (ResampleArgs), any i
+__device__ __forceinline__ float rs_x(const ResampleArgs& a, int64_t row, int64_t i) {
+    if (i < 0) return (a.hist && i >= -(int64_t)a.H) ? a.hist[row * a.H + a.H + i] : 0.0f;
+    if (i >= a.n_in) return 0.0f;
+    const int64_t t = i / a.in_block, r = i - t * a.in_block;
+    const int64_t at = row * a.stride + t * a.tick_stride + r;
+    return a.in16 ? (float)a.in16[at] * (1.0f / 32768.0f) : a.in[at];
+}
+
+__global__ __launch_bounds__(kRsMaxThreads) void k_resample(const ResampleArgs a, const int32_t tiles) {
+    extern __shared__ float s_x[];   // [a.span]: X(i_lo ..)
+    const int S = (int)blockDim.x, t = (int)threadIdx.x;
+    const int64_t row = blockIdx.x / (uint32_t)tiles;
+    const int64_t o0 = (int64_t)(blockIdx.x % (uint32_t)tiles) * kRsQ * S;
+    // c of the tile's first output, floor-divided by up (c > -down can be negative)
+    const int64_t cb = o0 * a.down + a.c0;
+    int64_t ib = cb / a.up, rb = cb - ib * a.up;
+    if (rb < 0) { rb += a.up; ib -= 1; }
+    const int64_t i_lo = ib - (a.J - 1);
+    {   // stage the span: the tick of the first sample once, then a compare per sample
+        const int64_t i_pos = i_lo > 0 ? i_lo : 0;
+        const int64_t t_lo = i_pos / a.in_block;
+        const int64_t base = row * a.stride;
+        for (int k = t; k < a.span; k += S) {
+            const int64_t i = i_lo + k;
+            float v = 0.0f;
+            if (i < 0) {
+                if (a.hist && i >= -(int64_t)a.H) v = a.hist[row * a.H + a.H + i];
+            } else if (i < a.n_in) {
+                int64_t tt = t_lo, r = i - t_lo * a.in_block;
+                if (r >= a.in_block) {
+                    const int64_t dt = r / a.in_block;
+                    tt += dt;
+                    r -= dt * a.in_block;
+                }
+                const int64_t at = base + tt * a.tick_stride + r;
+                v = a.in16 ? (float)a.in16[at] * (1.0f / 32768.0f) : a.in[at];
+            }
+            s_x[k] = v;
+        }
+    }
+    __syncthreads();
+    const uint32_t d0 = (uint32_t)t * (uint32_t)a.down + (uint32_t)rb;
+    const uint32_t idx0 = d0 / (uint32_t)a.up, p = d0 - idx0 * (uint32_t)a.up;
+    const uint32_t step = (uint32_t)((int64_t)S * a.down / a.up);   // exact: S is a multiple of up
+    const double* tp = a.taps + p;
+    double acc[kRsQ];
+#pragma unroll
+    for (int q = 0; q < kRsQ; ++q) acc[q] = 0.0;
+    uint32_t k = idx0;   // s_x[k] = X(i - j) for j = J - 1
+    for (int j = a.J - 1; j >= 0; --j, ++k) {
+        const double h = tp[(size_t)j * a.up];
+#pragma unroll
+        for (int q = 0; q < kRsQ; ++q) acc[q] = fma(h, (double)s_x[k + q * step], acc[q]);
+    }
+    float* o = a.out + row * a.out_stride;
+#pragma unroll
+    for (int q = 0; q < kRsQ; ++q) {
+        const int64_t n = o0 + t + (int64_t)q * S;
+        if (n < a.n_out) o[n] = n < a.n_zero ? 0.0f : (float)acc[q];
+    }
+}
+
+// one workgroup per row: read the new tail (it may reach into the old history), then write it
+__global__ __launch_bounds__(256) void k_resample_save(const ResampleArgs a, float* hist) {   // (hist == a.hist)
+    extern __shared__ float s_h[];   // [a.H]
+    const int64_t row = blockIdx.x;
+    for (int k = threadIdx.x; k < a.H; k += blockDim.x) s_h[k] = rs_x(a, row, a.n_in - a.H + k);
+    __syncthreads();
+    for (int k = threadIdx.x; k < a.H; k += blockDim.x) hist[row * a.H + k] = s_h[k];
+}
+
+int resample_threads(int32_t up) {
+    if (up <= 0 || up > kRsMaxThreads) return 0;
+    return up > 256 ? up : up * (256 / up);
+}
+
+int64_t resample_span(int32_t up, int32_t down, int32_t J, int32_t threads) {
+    const int64_t tile = (int64_t)kRsQ * threads;
+    return ((tile - 1) * down + up - 1) / up + J;
+}
+
+hipError_t launch_resample(const ResampleArgs& a, hipStream_t s) {
+    if (a.rows <= 0 || a.n_out <= 0) return hipSuccess;
+    if (a.threads <= 0 || a.threads % a.up || a.span > kRsMaxSpan ||
+        a.span != resample_span(a.up, a.down, a.J, a.threads) || a.in_block <= 0)
+        return hipErrorInvalidValue;
+    const int64_t tile = (int64_t)kRsQ * a.threads;
+    const int64_t tiles = (a.n_out + tile - 1) / tile;
+    if (tiles * a.rows > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_resample, dim3((unsigned)(tiles * a.rows)), dim3(a.threads), (size_t)a.span * sizeof(float), s,
+                       a, (int32_t)tiles);
+    return hipGetLastError();
+}
+
+hipError_t launch_resample_save(const ResampleArgs& a, float* hist, hipStream_t s) {
+    if (a.rows <= 0 || a.H <= 0) return hipSuccess;
+    if (a.H > kRsMaxSpan || a.in_block <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_resample_save, dim3(a.rows), dim3(256), (size_t)a.H * sizeof(float), s, a, hist);
+    return hipGetLastError();
+}
+
+}  // namespace ewk

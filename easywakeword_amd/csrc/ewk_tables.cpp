@@ -10,6 +10,7 @@
 #include <math.h>
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "ewk_internal.h"
@@ -208,6 +209,42 @@ void build_tables64(Tables64* t) {
         for (int k = lo; k <= hi && off < (int)(sizeof(t->mel_w) / sizeof(float)); ++k) t->mel_w[off++] = t->melw_dense[m * NBIN + k];
     }
     t->mel_off[NMEL] = off;
+}
+
+// Input-rate resampler: the filter of scipy.signal.resample_poly(x, up, down, window=("kaiser", 5.0))
+// (easywakeword_amd.audio.resample): half = 10 * max(up, down),
+// h = firwin(2 * half + 1, 1 / max(up, down), window=("kaiser", 5.0)) * up.
+static double bessel_i0(double x) {   // sum ((x/2)^k / k!)^2; x <= 5 here: 40 terms are past long double
+    const long double q = 0.25L * (long double)x * (long double)x;
+    long double term = 1.0L, sum = 1.0L;
+    for (int k = 1; k < 64; ++k) {
+        term *= q / ((long double)k * (long double)k);
+        sum += term;
+        if (term < 1e-22L * sum) break;
+    }
+    return (double)sum;
+}
+
+void resample_ratio(int32_t in_rate, int32_t out_rate, int32_t* up, int32_t* down) {
+    int64_t a = in_rate, b = out_rate;
+    while (b) { const int64_t t = a % b; a = b; b = t; }
+    *up = (int32_t)(out_rate / a);
+    *down = (int32_t)(in_rate / a);
+}
+
+void resample_taps(int32_t up, int32_t down, double* h) {
+    const int64_t mx = std::max(up, down), half = 10 * mx, n = 2 * half + 1;
+    const double cutoff = 1.0 / (double)mx, beta = 5.0, i0b = bessel_i0(beta);
+    long double sum = 0.0L;
+    for (int64_t k = 0; k < n; ++k) {
+        const double m = (double)(k - half);
+        const double y = kPi * (m == 0.0 ? 1e-20 : cutoff * m);       // numpy.sinc
+        const double r = m / (double)half;
+        const double w = bessel_i0(beta * sqrt(std::max(0.0, 1.0 - r * r))) / i0b;   // scipy.signal.windows.kaiser, sym
+        h[k] = cutoff * (sin(y) / y) * w;
+        sum += h[k];
+    }
+    for (int64_t k = 0; k < n; ++k) h[k] = h[k] / (double)sum * (double)up;   // unit DC gain, then * up
 }
 
 void table_window(double* w) { hann_periodic(w); }

@@ -108,7 +108,7 @@ class Engine:
 
     def profile_read(self, kind: int = 0):
         """(total_ms, launches) of the kernel family since the last read
-        (0 = fp32 scorer, 1 = fp64 re-scorer, 2 = gate)."""
+        (0 = fp32 scorer, 1 = fp64 re-scorer, 2 = gate, 3 = resampler)."""
         ms = C.c_double(0.0)
         n = C.c_int64(0)
         check(self._lib.ewk_profile_read(self._h, int(kind), C.byref(ms), C.byref(n)))
@@ -313,6 +313,26 @@ class Engine:
                                              out.ctypes.data_as(C.c_void_p), 0))
         return out
 
+    def resample(self, audio, orig_sr: int) -> np.ndarray:
+        """`audio` at orig_sr Hz -> 16 kHz float32 on the GPU: the arithmetic of
+        easywakeword_amd.audio.resample (polyphase Kaiser FIR, float64 accumulation),
+        ceil(n * 16000 / orig_sr) samples."""
+        a = _f32(audio)
+        out = np.zeros(-(-len(a) * FREQUENCY // int(orig_sr)) if int(orig_sr) > 0 else 0, np.float32)
+        n = C.c_int64(0)
+        check(self._lib.ewk_resample(self._h, a.ctypes.data_as(C.c_void_p), len(a), int(orig_sr),
+                                     out.ctypes.data_as(C.c_void_p), len(out), C.byref(n), 0))
+        return out[: n.value]
+
+    def resample_device(self, in_ptr: int, n_in: int, orig_sr: int, out_ptr: int, cap: int) -> int:
+        """Device-resident resample (float32 at in_ptr -> out_ptr, room for `cap` samples);
+        asynchronous on the engine's stream.  Returns the number of samples written."""
+        n = C.c_int64(0)
+        check(self._lib.ewk_resample(self._h, C.c_void_p(in_ptr or None), int(n_in), int(orig_sr),
+                                     C.c_void_p(out_ptr or None), int(cap), C.byref(n),
+                                     _lib.EWK_PCM_DEVICE | _lib.EWK_OUT_DEVICE))
+        return int(n.value)
+
     def score_device(self, pcm_ptr: int, offsets_ptr: int, lengths_ptr: int, n: int, mean_ptr: int,
                      std_ptr: int, score_ptr: int, match_ptr: int, stream: int = 0,
                      f32_candidates: bool = False) -> None:
@@ -347,31 +367,47 @@ class StreamEngine(Engine):
         self.block = int(self.config.block)
         self.ring_len = int(self.config.buffer_seconds) * FREQUENCY          # the reference ring
         self.sample_ring = int(self.config.ring_samples) or self.ring_len    # samples kept per stream
+        # the rate pushes arrive at (set_input_rate), its samples per tick and the delay of the 16 kHz stream
+        self.input_rate, self.input_block, self.input_delay = FREQUENCY, self.block, 0
+
+    # -- ingest at the source's own sample rate ---------------------------------
+    def set_input_rate(self, hz: int) -> None:
+        """From the next push on, blocks arrive at `hz` (e.g. 48000, 44100, 8000): input_block
+        samples per stream and tick, resampled to 16 kHz on the device with state carried from
+        push to push.  The 16 kHz stream (read_last, events) is audio.resample of the input
+        delayed by input_delay samples.  0 or 16000: off.  Clears the resampler's history;
+        ValueError for an int16 ring or a rate whose tick is not a whole number of samples."""
+        check(self._lib.ewk_set_input_rate(self._h, int(hz)))
+        r, b, d = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        check(self._lib.ewk_input_rate_info(self._h, C.byref(r), C.byref(b), C.byref(d)))
+        self.input_rate, self.input_block, self.input_delay = int(r.value), int(b.value), int(d.value)
 
     def push(self, blocks: np.ndarray) -> None:
-        """One tick: `blocks` is float32 [n_streams, block] (host)."""
+        """One tick: `blocks` is float32 [n_streams, input_block] (host)."""
         b = np.ascontiguousarray(blocks, dtype=np.float32)
-        if b.shape != (self.n_streams, self.block):
-            raise ValueError(f"expected blocks of shape {(self.n_streams, self.block)}, got {b.shape}")
-        check(self._lib.ewk_push(self._h, b.ctypes.data_as(C.c_void_p), self.block, 0))
+        if b.shape != (self.n_streams, self.input_block):
+            raise ValueError(f"expected blocks of shape {(self.n_streams, self.input_block)}, got {b.shape}")
+        check(self._lib.ewk_push(self._h, b.ctypes.data_as(C.c_void_p), self.input_block, 0))
 
     def push_many(self, pcm: np.ndarray) -> None:
-        """Several ticks: float32 [n_streams, n_ticks * block] (host)."""
+        """Several ticks: float32 [n_streams, n_ticks * input_block] (host)."""
         a = np.ascontiguousarray(pcm, dtype=np.float32)
-        if a.ndim != 2 or a.shape[0] != self.n_streams or a.shape[1] % self.block:
-            raise ValueError("pcm must be [n_streams, n_ticks*block]")
-        nt = a.shape[1] // self.block
+        if a.ndim != 2 or a.shape[0] != self.n_streams or a.shape[1] % self.input_block:
+            raise ValueError("pcm must be [n_streams, n_ticks*block]" if self.input_block == self.block else
+                             f"pcm must be [n_streams, n_ticks*{self.input_block}] at {self.input_rate} Hz")
+        nt = a.shape[1] // self.input_block
         if nt:
-            check(self._lib.ewk_push_many(self._h, a.ctypes.data_as(C.c_void_p), a.shape[1], self.block, nt, 0))
+            check(self._lib.ewk_push_many(self._h, a.ctypes.data_as(C.c_void_p), a.shape[1], self.input_block, nt, 0))
 
     def push_pcm16(self, pcm16: np.ndarray) -> None:
-        """Ticks of int16 PCM [n_streams, n_ticks * block] (host), decoded on the device."""
+        """Ticks of int16 PCM [n_streams, n_ticks * input_block] (host), decoded on the device."""
         a = np.ascontiguousarray(pcm16, dtype=np.int16)
-        if a.ndim != 2 or a.shape[0] != self.n_streams or a.shape[1] % self.block:
-            raise ValueError("pcm16 must be [n_streams, n_ticks*block]")
-        nt = a.shape[1] // self.block
+        if a.ndim != 2 or a.shape[0] != self.n_streams or a.shape[1] % self.input_block:
+            raise ValueError("pcm16 must be [n_streams, n_ticks*block]" if self.input_block == self.block else
+                             f"pcm16 must be [n_streams, n_ticks*{self.input_block}] at {self.input_rate} Hz")
+        nt = a.shape[1] // self.input_block
         if nt:
-            check(self._lib.ewk_push_many_pcm16(self._h, a.ctypes.data_as(C.c_void_p), a.shape[1], self.block,
+            check(self._lib.ewk_push_many_pcm16(self._h, a.ctypes.data_as(C.c_void_p), a.shape[1], self.input_block,
                                                 nt, 0))
 
     def normalize_events(self, events: np.ndarray) -> list:
@@ -403,7 +439,8 @@ class StreamEngine(Engine):
         return [out[int(o):int(o) + int(l)] for o, l in zip(offs, lengths)]
 
     def push_device(self, ptr: int, stride: int, tick_stride: int = 0, n_ticks: int = 1) -> None:
-        """Device-resident float32 ticks: stream s, tick t at ptr + 4 * (s * stride + t * tick_stride)."""
+        """Device-resident float32 ticks: stream s, tick t at ptr + 4 * (s * stride + t * tick_stride);
+        input_block samples each, strides in input samples (set_input_rate)."""
         check(self._lib.ewk_push_many(self._h, C.c_void_p(ptr), int(stride), int(tick_stride), int(n_ticks),
                                       _lib.EWK_PUSH_DEVICE))
 

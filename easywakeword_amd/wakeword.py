@@ -192,6 +192,11 @@ class SoundBuffer:
             source = _default_source(device)
         self.source = source
         self.engine = engine or StreamEngine(1, gpu=gpu, buffer_seconds=seconds, block=source.block, **cfg)
+        # a source at its own rate (ArraySource(rate=), WavSource(native_rate=True), MicSource(samplerate=)):
+        # its blocks are resampled on the device (StreamEngine.set_input_rate)
+        rate = int(getattr(source, "rate", FREQUENCY) or FREQUENCY)
+        if rate != FREQUENCY:
+            self.engine.set_input_rate(rate)
         self.source.start()
 
     def pump(self) -> np.ndarray:

@@ -333,11 +333,51 @@ int ewk_compact_positives(ewk_engine* e, const double* d_score, const uint8_t* d
  * host arrays unless EWK_PCM_DEVICE (then both are device memory, asynchronous). */
 int ewk_decode_pcm16(ewk_engine* e, const int16_t* in, int64_t n, float* out, int32_t flags);
 
+/* ---- ingest at the source's own sample rate: the device resampler ------------------ */
+/* The reference gets 16 kHz from PortAudio (sd.InputStream(samplerate=16000), wakeword.py:438-444)
+ * and from librosa.load(sr=16000); sources without either (network, files, decoders whose output
+ * is already in device memory) deliver 8, 44.1, 48 kHz.  The filter is the one of
+ * easywakeword_amd.audio.resample = scipy.signal.resample_poly(window=("kaiser", 5.0)):
+ * g = gcd(in, out), up = out / g, down = in / g, half = 10 * max(up, down),
+ * h = firwin(2 * half + 1, 1 / max(up, down), ("kaiser", 5.0)) * up, zero-phase:
+ * y[m] = sum_k h[k] * xu[m * down + half - k] with xu[i * up] = x[i], zeros beyond both ends of x;
+ * float64 accumulation over the taps of the output's phase, one rounding to float32. */
+/* The filter alone (host, no engine, no device): writes *up, *down and *n_taps = 2 * half + 1,
+ * then the taps (float64) when cap >= *n_taps -- else EWK_EINVAL (also for a rate <= 0). */
+int ewk_resample_design(int32_t in_rate, int32_t out_rate, double* taps, int32_t cap,
+                        int32_t* n_taps, int32_t* up, int32_t* down);
+/* A whole signal in_rate -> cfg.sample_rate: *n_out = ceil(n_in * out / in) samples, equal to
+ * audio.resample(x, in_rate, 16000) (EWK_EINVAL, with *n_out set, when cap is smaller).  in / out
+ * are host memory unless flags has EWK_PCM_DEVICE / EWK_OUT_DEVICE; asynchronous on the engine's
+ * stream when both are device memory.  Works on an engine without streams. */
+int ewk_resample(ewk_engine* e, const float* in, int64_t n_in, int32_t in_rate,
+                 float* out, int64_t cap, int64_t* n_out, int32_t flags);
+/* Streaming: from the next push on, every ewk_push / ewk_push_many / ewk_push_pcm16 /
+ * ewk_push_many_pcm16 reads in_block = block * down / up samples at in_rate per stream and tick
+ * (4800 at 48 kHz, 4410 at 44.1 kHz, 800 at 8 kHz for block 1600; stride and tick_stride count
+ * input samples), resamples them on the device with the last J + 1 input samples of each stream
+ * carried from push to push (J = floor(2 * half / up) + 1 taps per output) and hands the gate the
+ * 16 kHz block.  The zero-phase filter looks ahead, so the 16 kHz stream is the whole-signal
+ * resample y delayed by delay = ceil(half / down) samples: its sample n is y[n - delay], zero for
+ * n < delay (10 samples = 0.625 ms when downsampling, 20 from 8 kHz).  Events, ring_start, ticks,
+ * ewk_read_last / ewk_read_segment, the bank and the stream bank stay in the 16 kHz domain.
+ * in_rate 0 or cfg.sample_rate: off.  Waits for the pushes so far and clears the history (as
+ * ewk_reset_streams does; the rate stays set across a reset).  The first call allocates the
+ * history and one tick of resampled blocks (a longer ewk_push_many grows it), freed with the
+ * engine.  EWK_EINVAL: an engine without streams, an EWK_RING_I16 ring (resampled samples are not
+ * int16), block * down not a multiple of up (11,025 Hz with block 1600), a filter over the
+ * kernel's size (up > 1024, or more than 12,288 staged input samples per workgroup). */
+int ewk_set_input_rate(ewk_engine* e, int32_t in_rate);
+/* The rate in force with its samples per tick and delay (cfg.sample_rate, block, 0 when off);
+ * any pointer may be NULL. */
+int ewk_input_rate_info(ewk_engine* e, int32_t* in_rate, int32_t* in_block, int32_t* delay);
+
 /* ---- measurement ------------------------------------------------------------ */
 /* When enabled, every scorer / gate launch is bracketed by hipEvents on the
  * stream it runs on; ewk_profile_read resolves them (synchronizing) and returns
  * the summed device time and launch count per kernel family, then clears.
- * kind: 0 = fp32 MFCC scorer (k_score_f32), 1 = fp64 re-scorer, 2 = gate ticks. */
+ * kind: 0 = fp32 MFCC scorer (k_score_f32), 1 = fp64 re-scorer, 2 = gate ticks,
+ * 3 = resampler launches (ewk_resample, and the resample + history save of a push). */
 int ewk_profile_enable(ewk_engine* e, int32_t on);
 int ewk_profile_read(ewk_engine* e, int32_t kind, double* total_ms, int64_t* launches);
 
