@@ -60,6 +60,8 @@ EXPORTS = [
     "ewk_score_segments_bank", "ewk_score_segments_bank_device",
     "ewk_stream_bank_enable", "ewk_stream_bank_disable",
     "ewk_resample_design", "ewk_resample", "ewk_set_input_rate", "ewk_input_rate_info",
+    "ewk_push_streams", "ewk_push_streams_pcm16", "ewk_reset_stream_list", "ewk_stream_ticks",
+    "ewk_stream_bank_assign",
 ]
 
 
@@ -197,6 +199,12 @@ def load():
             "ewk_resample": (C.c_int, [_P, _P, C.c_int64, C.c_int32, _P, C.c_int64, _i64p, C.c_int32]),
             "ewk_set_input_rate": (C.c_int, [_P, C.c_int32]),
             "ewk_input_rate_info": (C.c_int, [_P, _i32p, _i32p, _i32p]),
+            "ewk_push_streams": (C.c_int, [_P, _i32p, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+            "ewk_push_streams_pcm16": (C.c_int, [_P, _i32p, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int32,
+                                                 C.c_int32]),
+            "ewk_reset_stream_list": (C.c_int, [_P, _i32p, C.c_int32]),
+            "ewk_stream_ticks": (C.c_int, [_P, _i32p, C.c_int32, _i64p]),
+            "ewk_stream_bank_assign": (C.c_int, [_P, _i32p, C.c_int32, _i32p]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)

@@ -176,6 +176,19 @@ struct ewk_engine {
     size_t h_stage_cap = 0;
     hipEvent_t h_stage_free = nullptr;   // recorded after the last DMA out of h_stage
     int64_t tick = 0;
+    // Stream lifecycle (ewk_push_streams / ewk_reset_stream_list).  A lockstep engine has one clock,
+    // `tick`.  The first subset push or list reset desynchronises it: stream s has then had
+    // tick + tick_delta[s] ticks (the host mirror of GateStream::tick; full pushes still only
+    // advance `tick`) and the gate runs every stream on its own clock.  ewk_reset_streams returns
+    // the engine to lockstep.  seen / seen_epoch: the duplicate test of an index list, O(n) per call.
+    bool desync = false;
+    std::vector<int64_t> tick_delta;   // [n_streams] once desynchronised
+    std::vector<uint32_t> seen;        // [n_streams]: the epoch of the call that last listed the stream
+    uint32_t seen_epoch = 0;
+    int32_t* h_ids = nullptr;          // pinned [2 * n_streams]: an index list (and its words) on the way to d_ids
+    DevBuf<int32_t> d_ids;             // [2 * n_streams]
+    hipEvent_t h_ids_free = nullptr;   // recorded after the last DMA out of h_ids
+    int64_t stream_tick(int32_t s) const { return tick + (desync ? tick_delta[s] : 0); }
     int32_t gate_stage = 0;
     int32_t gate_val_len = 0;       // per-wave LDS doubles of the gate (tree values, sort scratch)
 
@@ -193,6 +206,9 @@ struct ewk_engine {
     bool rs_fresh = true;   // no push since the history was cleared: the first `delay` outputs are zero
     int32_t rs_in_block = 0, rs_delay = 0;
     DevBuf<float> rs_hist, rs_out;
+    // the same per stream ([n_streams], device), in place of rs_fresh from the first subset push or
+    // list reset with a rate set: set where a stream's history was cleared, cleared by its next push
+    DevBuf<uint8_t> rs_flags;
 
     // measurement: (start, stop) event pairs per kernel family
     bool prof = false;
@@ -385,6 +401,10 @@ void ewk_destroy(ewk_engine* e) {
     e->rs_one.taps.release();
     e->rs_hist.release();
     e->rs_out.release();
+    e->rs_flags.release();
+    e->d_ids.release();
+    if (e->h_ids) (void)hipHostFree(e->h_ids);
+    if (e->h_ids_free) (void)hipEventDestroy(e->h_ids_free);
     (void)hipFree(e->d_ring);
     (void)hipFree(e->d_brms);
     (void)hipFree(e->d_sorted);
@@ -1109,10 +1129,78 @@ int ewk_reset_streams(ewk_engine* e) {
     if (e->sb_list.p) HIP_TRY(hipMemsetAsync(e->sb_list.p, 0, kEvListHdr * sizeof(int32_t), s));
     // (an input rate stays set; the resampler's history starts from silence again)
     if (e->rs_hist.p) HIP_TRY(hipMemsetAsync(e->rs_hist.p, 0, e->rs_hist.cap * sizeof(float), s));
+    if (e->rs_flags.p) HIP_TRY(hipMemsetAsync(e->rs_flags.p, 1, e->rs_flags.cap, s));
     e->rs_fresh = true;
     zero_event_state(e);
     HIP_TRY(hipStreamSynchronize(s));
     e->tick = 0;
+    e->desync = false;   // one clock again
+    std::vector<int64_t>().swap(e->tick_delta);
+    return EWK_OK;
+}
+
+// ---- stream lifecycle: index lists --------------------------------------------------
+// An index list as every call that takes one requires it: 1 <= n <= n_streams, every entry a
+// stream, none twice (two waves would run one stream).  Host only; changes nothing but `seen`.
+static int check_stream_list(ewk_engine* e, const int32_t* streams, int32_t n) {
+    if (!streams) return fail(EWK_EINVAL, "streams is NULL");
+    if (n < 1 || n > e->n_streams)
+        return fail(EWK_EINVAL, "a stream list holds 1.." + std::to_string(e->n_streams) + " streams, got " +
+                                    std::to_string(n));
+    if (e->seen.empty()) e->seen.assign((size_t)e->n_streams, 0);
+    if (++e->seen_epoch == 0) {   // (wrapped: forget every earlier call)
+        std::fill(e->seen.begin(), e->seen.end(), 0);
+        e->seen_epoch = 1;
+    }
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t s = streams[i];
+        if (s < 0 || s >= e->n_streams)
+            return fail(EWK_EINVAL, "streams[" + std::to_string(i) + "] = " + std::to_string(s) + " is outside [0, " +
+                                        std::to_string(e->n_streams) + ")");
+        if (e->seen[s] == e->seen_epoch)
+            return fail(EWK_EINVAL, "streams[" + std::to_string(i) + "]: stream " + std::to_string(s) +
+                                        " is listed twice");
+        e->seen[s] = e->seen_epoch;
+    }
+    return EWK_OK;
+}
+
+// The list (and `vals`, one per entry, when given) to the device on s through pinned staging:
+// the caller's arrays may die on return.  *d_list / *d_vals: where kernels enqueued on s after
+// this call find them, until the next call.
+static int stage_stream_list(ewk_engine* e, const int32_t* streams, const int32_t* vals, int32_t n, hipStream_t s,
+                             const int32_t** d_list, const int32_t** d_vals) {
+    const size_t cap = 2 * (size_t)e->n_streams;
+    if (!e->h_ids) {
+        HIP_TRY(hipHostMalloc((void**)&e->h_ids, cap * sizeof(int32_t), hipHostMallocDefault));
+        HIP_TRY(hipEventCreateWithFlags(&e->h_ids_free, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(e->h_ids_free, s));
+    }
+    HIP_TRY(e->d_ids.reserve(cap));
+    HIP_TRY(hipEventSynchronize(e->h_ids_free));   // the previous list has left the staging
+    memcpy(e->h_ids, streams, (size_t)n * sizeof(int32_t));
+    if (vals) memcpy(e->h_ids + e->n_streams, vals, (size_t)n * sizeof(int32_t));
+    HIP_TRY(hipMemcpyAsync(e->d_ids.p, e->h_ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (vals)
+        HIP_TRY(hipMemcpyAsync(e->d_ids.p + e->n_streams, e->h_ids + e->n_streams, (size_t)n * sizeof(int32_t),
+                               hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(e->h_ids_free, s));
+    *d_list = e->d_ids.p;
+    if (d_vals) *d_vals = e->d_ids.p + e->n_streams;
+    return EWK_OK;
+}
+
+// First subset push or list reset: every stream gets a clock of its own.  With a rate set, also
+// the per-stream fresh flags, from the engine-wide one.
+static int desynchronise(ewk_engine* e, hipStream_t s) {
+    if (!e->desync) {
+        e->tick_delta.assign((size_t)e->n_streams, 0);
+        e->desync = true;
+    }
+    if (e->rs_on && !e->rs_flags.p) {
+        HIP_TRY(e->rs_flags.reserve((size_t)e->n_streams));
+        HIP_TRY(hipMemsetAsync(e->rs_flags.p, e->rs_fresh ? 1 : 0, e->rs_flags.cap, s));
+    }
     return EWK_OK;
 }
 
@@ -1255,10 +1343,17 @@ int ewk_stream_bank_disable(ewk_engine* e) {
     return EWK_OK;
 }
 
+// streams == nullptr: a tick for every stream (row s of pcm is stream s); else rows 0..n_list-1
+// are the ticks of streams[0..n_list) (ewk_push_streams).
 static int push_impl(ewk_engine* e, const void* pcm_any, int64_t stride, int64_t tick_stride, int32_t n_ticks,
-                     int32_t flags, bool pcm16) {
+                     int32_t flags, bool pcm16, const int32_t* streams = nullptr, int32_t n_list = 0) {
     if (!e) return fail(EWK_EINVAL, "engine is NULL");
     if (e->n_streams <= 0) return fail(EWK_EINVAL, "engine has no streams");
+    if (streams || n_list) {   // (validated before anything is enqueued or changed)
+        int rc = check_stream_list(e, streams, n_list);
+        if (rc) return rc;
+    }
+    const int32_t rows = streams ? n_list : e->n_streams;
     if (!pcm_any) return fail(EWK_EINVAL, "pcm is NULL");
     if (n_ticks <= 0) return fail(EWK_EINVAL, "n_ticks must be positive");
     if (!pcm16 && e->ring_es == sizeof(int16_t))
@@ -1267,17 +1362,24 @@ static int push_impl(ewk_engine* e, const void* pcm_any, int64_t stride, int64_t
     const unsigned char* pcm = static_cast<const unsigned char*>(pcm_any);
     // with an input rate set (ewk_set_input_rate) a tick is in_block samples at that rate
     const int64_t in_block = e->rs_on ? e->rs_in_block : e->cfg.block;
-    if (stride < in_block && e->n_streams > 1)
+    if (stride < in_block && rows > 1)
         return fail(EWK_EINVAL, e->rs_on ? "stride must be >= the input block (ewk_input_rate_info)" : "stride must be >= block");
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = e->stream;
     const void* src = pcm_any;
     int64_t st_stride = stride, tk_stride = tick_stride;
+    const int32_t* d_list = nullptr;
+    if (streams) {
+        int rc = desynchronise(e, s);
+        if (rc) return rc;
+        rc = stage_stream_list(e, streams, nullptr, n_list, s, &d_list, nullptr);
+        if (rc) return rc;
+    }
     if (!(flags & EWK_PUSH_DEVICE)) {
         // Gather the caller's (pageable) blocks into pinned staging on the CPU, then
         // DMA asynchronously: the caller's buffer may die as soon as we return.
         const size_t per_stream = (size_t)n_ticks * in_block;
-        const size_t total = per_stream * e->n_streams;
+        const size_t total = per_stream * rows;
         if (e->h_stage_free) HIP_TRY(hipEventSynchronize(e->h_stage_free));   // previous DMA done
         if (total > e->h_stage_cap) {
             if (e->h_stage) HIP_TRY(hipHostFree(e->h_stage));
@@ -1287,7 +1389,7 @@ static int push_impl(ewk_engine* e, const void* pcm_any, int64_t stride, int64_t
             e->h_stage_cap = total;
         }
         if (!e->h_stage_free) HIP_TRY(hipEventCreateWithFlags(&e->h_stage_free, hipEventDisableTiming));
-        for (int32_t st = 0; st < e->n_streams; ++st)
+        for (int32_t st = 0; st < rows; ++st)
             for (int32_t t = 0; t < n_ticks; ++t)
                 memcpy(reinterpret_cast<unsigned char*>(e->h_stage) + ((size_t)st * per_stream + (size_t)t * in_block) * es,
                        pcm + ((size_t)st * stride + (size_t)t * tick_stride) * es, in_block * es);
@@ -1303,9 +1405,9 @@ static int push_impl(ewk_engine* e, const void* pcm_any, int64_t stride, int64_t
         // hand the gate float32 16 kHz blocks
         const ewk_engine::RsFilter& f = e->rs_in;
         const size_t per_stream = (size_t)n_ticks * e->cfg.block;
-        if (per_stream * e->n_streams > e->rs_out.cap) {
+        if (per_stream * rows > e->rs_out.cap) {
             HIP_TRY(hipStreamSynchronize(s));   // an earlier gate launch may still read the old buffer
-            HIP_TRY(e->rs_out.reserve(per_stream * e->n_streams));
+            HIP_TRY(e->rs_out.reserve(per_stream * rows));
         }
         ResampleArgs r;
         memset(&r, 0, sizeof(r));
@@ -1319,22 +1421,24 @@ static int push_impl(ewk_engine* e, const void* pcm_any, int64_t stride, int64_t
         r.out = e->rs_out.p;
         r.out_stride = (int64_t)per_stream;
         r.n_out = (int64_t)per_stream;
-        r.rows = e->n_streams;
+        r.rows = rows;
+        r.ids = d_list;
+        r.fresh = e->rs_flags.p;   // per stream once there are flags, else rs_fresh for all
         r.taps = f.taps.p;
         r.up = f.up;
         r.down = f.down;
         r.J = f.J;
         r.H = f.H;
         r.c0 = f.c0;
-        r.n_zero = e->rs_fresh ? e->rs_delay : 0;
+        r.n_zero = (e->rs_flags.p || e->rs_fresh) ? e->rs_delay : 0;
         r.threads = f.threads;
         r.span = f.span;
         {
             ProfScope ps(e, 3, s);
             HIP_TRY(launch_resample(r, s));
-            HIP_TRY(launch_resample_save(r, e->rs_hist.p, s));
+            HIP_TRY(launch_resample_save(r, e->rs_hist.p, e->rs_flags.p, s));
         }
-        e->rs_fresh = false;
+        if (!streams) e->rs_fresh = false;   // (a subset push made the flags: rs_fresh is not read again)
         src = e->rs_out.p;
         st_stride = (int64_t)per_stream;
         tk_stride = e->cfg.block;
@@ -1350,7 +1454,9 @@ static int push_impl(ewk_engine* e, const void* pcm_any, int64_t stride, int64_t
         g.stride = st_stride;
         g.tick_stride = tk_stride;
         g.n_ticks = nt;
-        g.n_streams = e->n_streams;
+        g.n_streams = rows;
+        g.ids = d_list;
+        g.own_clock = e->desync ? 1 : 0;
         g.tick0 = e->tick;
         g.ring = e->ring_f32();
         g.ring16 = e->ring_i16();
@@ -1389,7 +1495,8 @@ static int push_impl(ewk_engine* e, const void* pcm_any, int64_t stride, int64_t
             ProfScope ps(e, 2, s);
             HIP_TRY(launch_gate(g, s));
         }
-        e->tick += nt;
+        if (!streams) e->tick += nt;
+        else for (int32_t i = 0; i < n_list; ++i) e->tick_delta[streams[i]] += nt;
         if (e->overlap) {
             int32_t* snap = e->d_work + 4 + k;
             HIP_TRY(launch_snapshot(e->evc_bank(e->bank), snap, s));
@@ -1437,6 +1544,90 @@ int ewk_push_pcm16(ewk_engine* e, const int16_t* pcm, int64_t stride, int32_t fl
 int ewk_push_many_pcm16(ewk_engine* e, const int16_t* pcm, int64_t stride, int64_t tick_stride, int32_t n_ticks,
                         int32_t flags) {
     return push_impl(e, pcm, stride, tick_stride, n_ticks, flags, true);
+}
+
+// ---------------------------------------------------------------- stream lifecycle
+int ewk_push_streams(ewk_engine* e, const int32_t* streams, int32_t n, const float* pcm, int64_t stride,
+                     int64_t tick_stride, int32_t n_ticks, int32_t flags) {
+    if (e && !streams) return fail(EWK_EINVAL, "streams is NULL");
+    return push_impl(e, pcm, stride, tick_stride, n_ticks, flags, false, streams, n);
+}
+
+int ewk_push_streams_pcm16(ewk_engine* e, const int32_t* streams, int32_t n, const int16_t* pcm, int64_t stride,
+                           int64_t tick_stride, int32_t n_ticks, int32_t flags) {
+    if (e && !streams) return fail(EWK_EINVAL, "streams is NULL");
+    return push_impl(e, pcm, stride, tick_stride, n_ticks, flags, true, streams, n);
+}
+
+int ewk_reset_stream_list(ewk_engine* e, const int32_t* streams, int32_t n) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (e->n_streams <= 0) return fail(EWK_EINVAL, "engine has no streams");
+    int rc = check_stream_list(e, streams, n);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    HIP_TRY(join_scoring(e, s));   // (overlap mode: the scorer may still read these ring rows)
+    rc = desynchronise(e, s);
+    if (rc) return rc;
+    ResetListArgs a;
+    memset(&a, 0, sizeof(a));
+    rc = stage_stream_list(e, streams, nullptr, n, s, &a.ids, nullptr);
+    if (rc) return rc;
+    a.n = n;
+    a.ring = static_cast<unsigned char*>(e->d_ring);
+    a.row_bytes = e->sring_len * (int64_t)e->ring_es;
+    a.block_rms = e->d_brms;
+    a.n_blocks = e->n_blocks;
+    a.st = e->d_st;
+    a.init_threshold = e->cfg.initial_threshold;
+    if (e->rs_on) {   // (a rate set earlier and switched off again: set_input_rate clears every row)
+        a.hist = e->rs_hist.p;
+        a.H = e->rs_in.H;
+        a.fresh = e->rs_flags.p;
+    }
+    HIP_TRY(launch_reset_list(a, s));
+    for (int32_t i = 0; i < n; ++i) e->tick_delta[streams[i]] = -e->tick;
+    return EWK_OK;
+}
+
+int ewk_stream_ticks(ewk_engine* e, const int32_t* streams, int32_t n, int64_t* out) {
+    if (!e || !out) return fail(EWK_EINVAL, "NULL argument");
+    if (n < 0 || n > e->n_streams)
+        return fail(EWK_EINVAL, "n must be in [0, " + std::to_string(e->n_streams) + "]");
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t s = streams ? streams[i] : i;
+        if (s < 0 || s >= e->n_streams)
+            return fail(EWK_EINVAL, "streams[" + std::to_string(i) + "] = " + std::to_string(s) + " is outside [0, " +
+                                        std::to_string(e->n_streams) + ")");
+    }
+    for (int32_t i = 0; i < n; ++i) out[i] = e->stream_tick(streams ? streams[i] : i);
+    return EWK_OK;
+}
+
+int ewk_stream_bank_assign(ewk_engine* e, const int32_t* streams, int32_t n, const int32_t* words) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (!e->sbank_on) return fail(EWK_EINVAL, "the stream bank is off (ewk_stream_bank_enable)");
+    int rc = check_stream_list(e, streams, n);
+    if (rc) return rc;
+    if (!words) return fail(EWK_EINVAL, "words is NULL");
+    const int32_t n_words = (int32_t)e->bank_first.size() - 1;
+    for (int32_t i = 0; i < n; ++i)
+        if (words[i] < 0 || words[i] >= n_words)
+            return fail(EWK_EINVAL, "word index " + std::to_string(words[i]) + " of stream " +
+                                        std::to_string(streams[i]) + " is outside [0, " + std::to_string(n_words) + ")");
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    HIP_TRY(join_scoring(e, s));   // (overlap mode: a scoring pass in flight still reads the words)
+    if (!e->sbank_words) {   // enabled with word 0 for every stream: the array, all zeros
+        HIP_TRY(e->sb_word.reserve((size_t)e->n_streams));
+        HIP_TRY(hipMemsetAsync(e->sb_word.p, 0, (size_t)e->n_streams * sizeof(int32_t), s));
+        e->sbank_words = true;
+    }
+    const int32_t *d_list = nullptr, *d_vals = nullptr;
+    rc = stage_stream_list(e, streams, words, n, s, &d_list, &d_vals);
+    if (rc) return rc;
+    HIP_TRY(launch_scatter_i32(e->sb_word.p, d_list, d_vals, n, s));
+    return EWK_OK;
 }
 
 // ---------------------------------------------------------------- level-3 input / PCM16 decode
@@ -1523,19 +1714,20 @@ int ewk_normalize_events(ewk_engine* e, const ewk_event* events, int32_t n, doub
             ev.ring_start < 0 || ev.ring_start >= e->sring_len)
             return fail(EWK_EINVAL, "event " + std::to_string(i) + " outside the rings");
         // The segment is the last nreq >= length samples before the write position of its
-        // tick (ewk_gate.hip, the cut), and every later tick writes one block: it is intact
-        // while nreq + (ticks since) * block <= ring.  (The write position after tick k is
-        // k * block mod ring for every stream.)
+        // tick (ewk_gate.hip, the cut), and every later tick of its stream writes one block: it
+        // is intact while nreq + (ticks since) * block <= ring.  (The write position after tick k
+        // is k * block mod ring for every stream, k counted on the stream's own clock.)
         const int64_t Rs = e->sring_len, blk = e->cfg.block;
-        if (ev.tick < 0 || ev.tick > e->tick)
+        const int64_t now = e->stream_tick(ev.stream);   // its stream's clock (the engine's in lockstep)
+        if (ev.tick < 0 || ev.tick > now)
             return fail(EWK_EINVAL, "event " + std::to_string(i) + " is from a tick this engine has not pushed");
         int64_t nreq = ((ev.tick % Rs) * (blk % Rs) % Rs - ev.ring_start) % Rs;
         if (nreq < 0) nreq += Rs;
         if (nreq == 0 && ev.length > 0) nreq = Rs;
-        if (nreq + (e->tick - ev.tick) * blk > Rs)
+        if (nreq + (now - ev.tick) * blk > Rs)
             return fail(EWK_EOVERWRITTEN, "event " + std::to_string(i) + " (tick " + std::to_string(ev.tick) +
                                         "): the ring has overwritten its samples since (now tick " +
-                                        std::to_string(e->tick) + "); read positives right after their poll");
+                                        std::to_string(now) + "); read positives right after their poll");
     }
     HIP_TRY(hipSetDevice(e->device));
     return normalize_impl(e, nullptr, nullptr, nullptr, events, n, out, flags);
@@ -1722,6 +1914,10 @@ int ewk_set_input_rate(ewk_engine* e, int32_t in_rate) {
     if (nh > e->rs_hist.cap) HIP_TRY(e->rs_hist.reserve(nh));
     HIP_TRY(hipMemset(e->rs_hist.p, 0, e->rs_hist.cap * sizeof(float)));
     HIP_TRY(e->rs_out.reserve((size_t)e->n_streams * e->cfg.block));
+    if (e->desync || e->rs_flags.p) {   // streams on their own clocks: every one starts fresh
+        HIP_TRY(e->rs_flags.reserve((size_t)e->n_streams));
+        HIP_TRY(hipMemset(e->rs_flags.p, 1, e->rs_flags.cap));
+    }
     e->rs_in_block = (int32_t)((int64_t)e->cfg.block * down / up);
     e->rs_delay = (int32_t)((f.half + down - 1) / down);
     e->rs_fresh = true;

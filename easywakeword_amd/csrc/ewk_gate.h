@@ -88,9 +88,33 @@ struct GateArgs {
     int32_t* ev_dropped;
     int32_t ev_cap;
     int32_t ev_base0;         // the bank's epoch base: event slot = count - ev_base0 (wrapping)
+    // Subset pushes (ewk_push_streams): row r of pcm is stream ids[r], n_streams counts the rows;
+    // nullptr: row r is stream r.  Everything but the samples' source is addressed by the stream.
+    const int32_t* ids;
+    int32_t own_clock;        // 1: every stream counts from its own GateStream::tick (tick0 unused)
+    int32_t pad1;
 };
 
 hipError_t launch_gate(const GateArgs& g, hipStream_t s);
+// ewk_reset_stream_list: streams ids[0..n) back to the state ewk_reset_streams gives every stream,
+// in one launch: ring row zeroed with k_ring_zero's agent-scope stores, block RMS row zeroed,
+// GateStream = init, and with a resampler its history row zeroed and its fresh flag set.
+struct ResetListArgs {
+    const int32_t* ids;
+    int32_t n;
+    unsigned char* ring;     // [n_streams][row_bytes]
+    int64_t row_bytes;       // sring_len * sample size (any multiple of the sample size)
+    double* block_rms;       // [n_streams][n_blocks]
+    int32_t n_blocks;
+    GateStream* st;
+    double init_threshold;   // ewk_config.initial_threshold
+    float* hist;            // nullptr or [n_streams][H]
+    int32_t H;
+    uint8_t* fresh;          // nullptr or [n_streams]
+};
+hipError_t launch_reset_list(const ResetListArgs& a, hipStream_t s);
+// dst[ids[i]] = vals[i], i < n (ewk_stream_bank_assign)
+hipError_t launch_scatter_i32(int32_t* dst, const int32_t* ids, const int32_t* vals, int32_t n, hipStream_t s);
 hipError_t launch_reenter(GateStream* st, int32_t first, int32_t n, double tick_seconds, hipStream_t s);
 // Zero a ring with agent-scope (sc1) stores: the lines go to memory and are dropped from the
 // writing XCD's L2, so no cached copy of the initial zeros outlives the gate's first writes.

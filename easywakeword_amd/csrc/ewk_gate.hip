@@ -489,7 +489,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGateWavesP
     // issued its stage reads, so its HBM latency overlaps this stream's FSM and stores
     // (readfirstlane: the compiler then knows the stream, hence its state, is wave-uniform --
     // scalar loads into SGPRs instead of a copy of GateStream in every lane's VGPRs)
-    int s = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + wave);
+    // r: the wave's row of the launch (where its samples come from); s: the stream that row
+    // feeds (g.ids, subset pushes), which addresses everything else.  Both wave-uniform.
+    int r = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + wave);
+    const int32_t* __restrict__ ids = g.ids;
     const int wstride = (int)gridDim.x * 4;
     constexpr int kStageEs = DMA == 3 ? 2 : 4;   // int16 stage for the vector int16 path
     const size_t per_wave = gate_wave_lds(g.val_len, g.stage, kStageEs);
@@ -507,7 +510,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGateWavesP
         for (int i = threadIdx.x; i < 2 * kPieces; i += blockDim.x) dst[i] = i < kPieces ? src0[i] : src1[i - kPieces];
         __syncthreads();
     }
-    if (s >= g.n_streams) return;
+    if (r >= g.n_streams) return;
+    int s = ids ? __builtin_amdgcn_readfirstlane(ids[r]) : r;
     unsigned char* w = smem + wave * per_wave;
     double* val = reinterpret_cast<double*>(w);
     float* stage = reinterpret_cast<float*>(w + (((size_t)g.val_len * 8 + 15) & ~(size_t)15));
@@ -526,7 +530,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGateWavesP
     // the first tick's samples are requested before the state: no load waits on another
     float xin[kIngestLoads];
     auto load_chunk = [&](int t, int c0) {
-        const int64_t so = (int64_t)s * g.stride + (int64_t)t * g.tick_stride;
+        const int64_t so = (int64_t)r * g.stride + (int64_t)t * g.tick_stride;
 #pragma unroll
         for (int m = 0; m < kIngestLoads; ++m) {
             const int i = c0 + lane + 64 * m;
@@ -568,13 +572,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGateWavesP
                                                  4, 0, 0);
         }
     };
-    if (dma) dma_tick(s, 0);
-    else if (DMA == 3) load_vec(s, 0);
+    if (dma) dma_tick(r, 0);
+    else if (DMA == 3) load_vec(r, 0);
     else load_chunk(0, 0);
     for (;;) {
     float* ring = g.ring ? g.ring + (int64_t)s * Rs : nullptr;
     int16_t* ring16 = g.ring16 ? g.ring16 + (int64_t)s * Rs : nullptr;   // PCM16 pushes only (host-checked)
     GateStream st = g.st[s];
+    const int64_t tick0 = g.own_clock ? st.tick : g.tick0;   // the stream's own clock, or the engine's (equal in lockstep)
     double* grms = g.block_rms + (int64_t)s * nb;
     double* sorted2 = g.sorted_rms + (int64_t)s * 2 * nb;
     const PwTree* tbf = trees + kTreeBlockFull;
@@ -594,7 +599,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGateWavesP
     }
 
     for (int t = 0; t < g.n_ticks; ++t) {
-        const int64_t tick = g.tick0 + t + 1;                    // tick being delivered
+        const int64_t tick = tick0 + t + 1;                      // tick being delivered
         const double t_prev = (double)(tick - 1) * g.tick_seconds;
         // start()-mode re-entry (TimeoutError -> _detect_word again), before the sleep
         if (st.started && g.reentry_timeout > 0.0 && t_prev - st.start_time > g.reentry_timeout) {
@@ -675,7 +680,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGateWavesP
                     if (staged) *reinterpret_cast<u32x4*>(stage16 + i0) = w;   // the int16 samples as delivered
                 }
             }
-            if (t + 1 < g.n_ticks) load_vec(s, t + 1);   // next tick's samples, in flight during this tick
+            if (t + 1 < g.n_ticks) load_vec(r, t + 1);   // next tick's samples, in flight during this tick
         }
         for (int c0 = 0; c0 < ((dma || DMA == 3) ? 0 : fs); c0 += 64 * kIngestLoads) {
             if (c0 > 0) load_chunk(t, c0);
@@ -822,10 +827,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGateWavesP
         }
         if (dma && t + 1 < g.n_ticks) {   // the stage's last reader (a3) has issued its reads
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            dma_tick(s, t + 1);
-        } else if (dma && s + wstride < g.n_streams) {   // last tick: the next stream's first
+            dma_tick(r, t + 1);
+        } else if (dma && r + wstride < g.n_streams) {   // last tick: the next row's first
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            dma_tick(s + wstride, 0);
+            dma_tick(r + wstride, 0);
         }
         st.last_silent = silent;
         st.tick = tick;
@@ -907,9 +912,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGateWavesP
         }
     }
     if (lane == 0) g.st[s] = st;
-    s += wstride;
-    if (s >= g.n_streams) break;
-    if (DMA == 3) load_vec(s, 0);
+    r += wstride;
+    if (r >= g.n_streams) break;
+    s = ids ? __builtin_amdgcn_readfirstlane(ids[r]) : r;
+    if (DMA == 3) load_vec(r, 0);
     else if (!dma) load_chunk(0, 0);
     }
 }
@@ -944,6 +950,60 @@ hipError_t launch_ring_zero(void* p, size_t bytes, hipStream_t s) {
     const size_t n8 = bytes / 8;
     const unsigned grid = (unsigned)std::min<size_t>(4096, (n8 + 255) / 256);
     hipLaunchKernelGGL(k_ring_zero, dim3(grid), dim3(256), 0, s, static_cast<uint64_t*>(p), n8);
+    return hipGetLastError();
+}
+
+// ewk_reset_stream_list: workgroup (i, c) zeroes piece c of stream ids[i]'s ring row with the
+// stores of k_ring_zero (for its reason); piece 0 also clears the block RMS row, the state, the
+// resampler history row and sets the fresh flag.  A row starts at a multiple of the sample size
+// only, so the bytes before the first and after the last 8-byte boundary go in 2-byte stores.
+constexpr int kResetPiece = 32768;   // ring bytes per workgroup
+__global__ __launch_bounds__(256) void k_reset_list(const ResetListArgs a, const int32_t pieces) {
+    const int i = (int)(blockIdx.x / (uint32_t)pieces), c = (int)(blockIdx.x % (uint32_t)pieces);
+    const int64_t sid = a.ids[i];
+    const uintptr_t b0 = (uintptr_t)(a.ring + sid * a.row_bytes), b1 = b0 + (uintptr_t)a.row_bytes;
+    const uintptr_t up0 = (b0 + 7) & ~(uintptr_t)7, dn1 = b1 & ~(uintptr_t)7;
+    const uintptr_t a0 = up0 < b1 ? up0 : b1, a1 = dn1 > a0 ? dn1 : a0;   // [a0, a1): the whole 8-byte words
+    {
+        const uintptr_t p0 = a0 + (uintptr_t)c * kResetPiece, p1 = p0 + kResetPiece < a1 ? p0 + kResetPiece : a1;
+        for (uintptr_t p = p0 + 8 * (uintptr_t)threadIdx.x; p < p1; p += 8 * 256)
+            __hip_atomic_store(reinterpret_cast<uint64_t*>(p), (uint64_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (c != 0) return;
+    {   // (fewer than 4 + 4 two-byte pieces)
+        const uintptr_t p = threadIdx.x < 4 ? b0 + 2 * (uintptr_t)threadIdx.x : a1 + 2 * ((uintptr_t)threadIdx.x - 4);
+        const bool in = threadIdx.x < 4 ? p < a0 : (threadIdx.x < 8 && p < b1);
+        if (in) __hip_atomic_store(reinterpret_cast<uint16_t*>(p), (uint16_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    for (int k = threadIdx.x; k < a.n_blocks; k += blockDim.x) a.block_rms[sid * a.n_blocks + k] = 0.0;
+    if (a.hist)
+        for (int k = threadIdx.x; k < a.H; k += blockDim.x) a.hist[sid * a.H + k] = 0.0f;
+    if (threadIdx.x == 0) {
+        GateStream z = {};   // (ewk_reset_streams' initial state)
+        z.threshold = a.init_threshold;
+        z.last_silent = 1;
+        a.st[sid] = z;
+        if (a.fresh) a.fresh[sid] = 1;
+    }
+}
+
+hipError_t launch_reset_list(const ResetListArgs& a, hipStream_t s) {
+    if (a.n <= 0) return hipSuccess;
+    if (a.row_bytes % 2 || ((uintptr_t)a.ring & 7)) return hipErrorInvalidValue;
+    const int64_t pieces = std::max<int64_t>(1, (a.row_bytes + kResetPiece - 1) / kResetPiece);
+    if (pieces * a.n > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_reset_list, dim3((unsigned)(pieces * a.n)), dim3(256), 0, s, a, (int32_t)pieces);
+    return hipGetLastError();
+}
+
+__global__ void k_scatter_i32(int32_t* dst, const int32_t* ids, const int32_t* vals, int32_t n) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i < n) dst[ids[i]] = vals[i];
+}
+
+hipError_t launch_scatter_i32(int32_t* dst, const int32_t* ids, const int32_t* vals, int32_t n, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_scatter_i32, dim3((n + 255) / 256), dim3(256), 0, s, dst, ids, vals, n);
     return hipGetLastError();
 }
 

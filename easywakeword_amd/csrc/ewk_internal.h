@@ -279,13 +279,19 @@ struct ResampleArgs {
     int64_t n_zero;           // outputs n < n_zero are zero (a stream's first `delay` samples)
     int32_t threads;          // resample_threads(up)
     int32_t span;             // resample_span(up, down, J, threads) <= kRsMaxSpan
+    // subset pushes (ewk_push_streams): row r is stream ids[r] -- its history row and fresh flag;
+    // nullptr: row r is stream r
+    const int32_t* ids;
+    // nullptr: n_zero holds for every row; else [streams] and only for the streams flagged (no push
+    // since their history was cleared); launch_resample_save clears the flags of its rows
+    const uint8_t* fresh;
 };
 int resample_threads(int32_t up);   // workgroup size: a multiple of up (0: up > kRsMaxThreads)
 int64_t resample_span(int32_t up, int32_t down, int32_t J, int32_t threads);
 hipError_t launch_resample(const ResampleArgs& a, hipStream_t s);
 // hist[r][k] = X(n_in - H + k): the tail of a push, saved once every workgroup of launch_resample
-// has read the old one (stream order)
-hipError_t launch_resample_save(const ResampleArgs& a, float* hist, hipStream_t s);
+// has read the old one (stream order); fresh: nullptr or a.fresh
+hipError_t launch_resample_save(const ResampleArgs& a, float* hist, uint8_t* fresh, hipStream_t s);
 
 // ewk_gather.hip: positives compaction (scratch: 2 * compact_blocks(n) int32)
 int compact_blocks(int32_t n);

@@ -14,8 +14,8 @@
 namespace ewk {
 
 // X(i) of a row (ResampleArgs), any i
-__device__ __forceinline__ float rs_x(const ResampleArgs& a, int64_t row, int64_t i) {
-    if (i < 0) return (a.hist && i >= -(int64_t)a.H) ? a.hist[row * a.H + a.H + i] : 0.0f;
+__device__ __forceinline__ float rs_x(const ResampleArgs& a, int64_t row, int64_t hrow, int64_t i) {
+    if (i < 0) return (a.hist && i >= -(int64_t)a.H) ? a.hist[hrow * a.H + a.H + i] : 0.0f;
     if (i >= a.n_in) return 0.0f;
     const int64_t t = i / a.in_block, r = i - t * a.in_block;
     const int64_t at = row * a.stride + t * a.tick_stride + r;
@@ -26,6 +26,7 @@ __global__ __launch_bounds__(kRsMaxThreads) void k_resample(const ResampleArgs a
     extern __shared__ float s_x[];   // [a.span]: X(i_lo ..)
     const int S = (int)blockDim.x, t = (int)threadIdx.x;
     const int64_t row = blockIdx.x / (uint32_t)tiles;
+    const int64_t hrow = a.ids ? a.ids[row] : row;   // the stream of this row: its history and fresh flag
     const int64_t o0 = (int64_t)(blockIdx.x % (uint32_t)tiles) * kRsQ * S;
     // c of the tile's first output, floor-divided by up (c > -down can be negative)
     const int64_t cb = o0 * a.down + a.c0;
@@ -40,7 +41,7 @@ __global__ __launch_bounds__(kRsMaxThreads) void k_resample(const ResampleArgs a
             const int64_t i = i_lo + k;
             float v = 0.0f;
             if (i < 0) {
-                if (a.hist && i >= -(int64_t)a.H) v = a.hist[row * a.H + a.H + i];
+                if (a.hist && i >= -(int64_t)a.H) v = a.hist[hrow * a.H + a.H + i];
             } else if (i < a.n_in) {
                 int64_t tt = t_lo, r = i - t_lo * a.in_block;
                 if (r >= a.in_block) {
@@ -69,20 +70,24 @@ __global__ __launch_bounds__(kRsMaxThreads) void k_resample(const ResampleArgs a
         for (int q = 0; q < kRsQ; ++q) acc[q] = fma(h, (double)s_x[k + q * step], acc[q]);
     }
     float* o = a.out + row * a.out_stride;
+    const int64_t n_zero = (a.fresh && !a.fresh[hrow]) ? 0 : a.n_zero;
 #pragma unroll
     for (int q = 0; q < kRsQ; ++q) {
         const int64_t n = o0 + t + (int64_t)q * S;
-        if (n < a.n_out) o[n] = n < a.n_zero ? 0.0f : (float)acc[q];
+        if (n < a.n_out) o[n] = n < n_zero ? 0.0f : (float)acc[q];
     }
 }
 
-// one workgroup per row: read the new tail (it may reach into the old history), then write it
-__global__ __launch_bounds__(256) void k_resample_save(const ResampleArgs a, float* hist) {   // (hist == a.hist)
+// one workgroup per row: read the new tail (it may reach into the old history), then write it;
+// the row's stream has had a push now (its fresh flag)
+__global__ __launch_bounds__(256) void k_resample_save(const ResampleArgs a, float* hist, uint8_t* fresh) {   // (hist == a.hist, fresh == a.fresh)
     extern __shared__ float s_h[];   // [a.H]
     const int64_t row = blockIdx.x;
-    for (int k = threadIdx.x; k < a.H; k += blockDim.x) s_h[k] = rs_x(a, row, a.n_in - a.H + k);
+    const int64_t hrow = a.ids ? a.ids[row] : row;
+    for (int k = threadIdx.x; k < a.H; k += blockDim.x) s_h[k] = rs_x(a, row, hrow, a.n_in - a.H + k);
     __syncthreads();
-    for (int k = threadIdx.x; k < a.H; k += blockDim.x) hist[row * a.H + k] = s_h[k];
+    for (int k = threadIdx.x; k < a.H; k += blockDim.x) hist[hrow * a.H + k] = s_h[k];
+    if (fresh && threadIdx.x == 0) fresh[hrow] = 0;
 }
 
 int resample_threads(int32_t up) {
@@ -108,10 +113,10 @@ hipError_t launch_resample(const ResampleArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_resample_save(const ResampleArgs& a, float* hist, hipStream_t s) {
+hipError_t launch_resample_save(const ResampleArgs& a, float* hist, uint8_t* fresh, hipStream_t s) {
     if (a.rows <= 0 || a.H <= 0) return hipSuccess;
     if (a.H > kRsMaxSpan || a.in_block <= 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_resample_save, dim3(a.rows), dim3(256), (size_t)a.H * sizeof(float), s, a, hist);
+    hipLaunchKernelGGL(k_resample_save, dim3(a.rows), dim3(256), (size_t)a.H * sizeof(float), s, a, hist, fresh);
     return hipGetLastError();
 }
 

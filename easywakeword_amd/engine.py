@@ -482,6 +482,75 @@ class StreamEngine(Engine):
     def reset(self) -> None:
         check(self._lib.ewk_reset_streams(self._h))
 
+    # -- stream lifecycle: push and reset individual streams -----------------------
+    def _stream_list(self, streams) -> np.ndarray:
+        s = np.ascontiguousarray(streams, dtype=np.int32).reshape(-1)
+        if s.size < 1 or s.size > self.n_streams:
+            raise ValueError(f"a stream list holds 1..{self.n_streams} streams, got {s.size}")
+        return s
+
+    def _push_streams(self, fn, streams, a: np.ndarray, what: str) -> None:
+        s = self._stream_list(streams)
+        if a.ndim != 2 or a.shape[0] != s.size or a.shape[1] % self.input_block:
+            raise ValueError(f"{what} must be [len(streams), n_ticks*block]" if self.input_block == self.block else
+                             f"{what} must be [len(streams), n_ticks*{self.input_block}] at {self.input_rate} Hz")
+        nt = a.shape[1] // self.input_block
+        if nt:
+            check(fn(self._h, _lib.i32ptr(s), s.size, a.ctypes.data_as(C.c_void_p), a.shape[1], self.input_block,
+                     nt, 0))
+
+    def push_streams(self, streams, pcm: np.ndarray) -> None:
+        """Ticks for a subset of the streams: row i of `pcm`, float32 [len(streams), n_ticks *
+        input_block] (host), goes to stream streams[i].  Every stream runs on its own clock (ticks
+        delivered to it since creation or its last reset): its events are those of a one-stream
+        engine fed the same blocks.  ValueError for an empty list, an index out of range or listed
+        twice; nothing is delivered then."""
+        self._push_streams(self._lib.ewk_push_streams, streams, np.ascontiguousarray(pcm, dtype=np.float32), "pcm")
+
+    def push_streams_pcm16(self, streams, pcm16: np.ndarray) -> None:
+        """push_streams with int16 PCM [len(streams), n_ticks * input_block] (host)."""
+        self._push_streams(self._lib.ewk_push_streams_pcm16, streams, np.ascontiguousarray(pcm16, dtype=np.int16),
+                           "pcm16")
+
+    def push_streams_device(self, streams, ptr: int, stride: int, tick_stride: int = 0, n_ticks: int = 1,
+                            pcm16: bool = False) -> None:
+        """Device-resident ticks for a subset: row i, tick t at ptr + es * (i * stride + t * tick_stride)
+        (es = 4, or 2 with pcm16=True) goes to stream streams[i].  `streams` stays a host list."""
+        s = self._stream_list(streams)
+        fn = self._lib.ewk_push_streams_pcm16 if pcm16 else self._lib.ewk_push_streams
+        check(fn(self._h, _lib.i32ptr(s), s.size, C.c_void_p(ptr), int(stride), int(tick_stride), int(n_ticks),
+                 _lib.EWK_PUSH_DEVICE))
+
+    def reset_streams(self, streams) -> None:
+        """The listed streams back to the state of a new engine (ring, threshold, FSM, tick 0,
+        resampler history); the others are untouched.  Stream-ordered, no wait.  Poll first: events
+        of these streams already queued keep their scores but lose their samples."""
+        s = self._stream_list(streams)
+        check(self._lib.ewk_reset_stream_list(self._h, _lib.i32ptr(s), s.size))
+
+    def stream_ticks(self, streams=None) -> np.ndarray:
+        """Ticks delivered to each listed stream (None: all) since creation or its last reset
+        (int64; host bookkeeping, no wait)."""
+        if streams is None:
+            out = np.zeros(self.n_streams, np.int64)
+            check(self._lib.ewk_stream_ticks(self._h, None, self.n_streams, _lib.i64ptr(out)))
+            return out
+        s = np.ascontiguousarray(streams, dtype=np.int32).reshape(-1)
+        out = np.zeros(s.size, np.int64)
+        if s.size > self.n_streams:
+            raise ValueError(f"{s.size} streams listed, the engine has {self.n_streams}")
+        check(self._lib.ewk_stream_ticks(self._h, _lib.i32ptr(s), s.size, _lib.i64ptr(out)))
+        return out
+
+    def assign_stream_words(self, streams, words) -> None:
+        """With the stream bank on (set_stream_bank): stream streams[i] listens for word words[i]
+        from the next push on; earlier events keep the word they were scored with."""
+        s = self._stream_list(streams)
+        w = np.ascontiguousarray(words, dtype=np.int32).reshape(-1)
+        if w.size != s.size:
+            raise ValueError(f"{w.size} word indices for {s.size} streams")
+        check(self._lib.ewk_stream_bank_assign(self._h, _lib.i32ptr(s), s.size, _lib.i32ptr(w)))
+
     # -- stream bank: gated events against many references, per stream ------------
     def set_stream_bank(self, stream_word=None) -> None:
         """From the next push on, every gated event of stream s is scored on the device against

@@ -279,6 +279,49 @@ int ewk_read_segment(ewk_engine* e, int32_t stream, int64_t ring_start, int32_t 
 /* Reset all stream state (ring, threshold, FSM, event queue).  A stream bank stays enabled. */
 int ewk_reset_streams(ewk_engine* e);
 
+/* ---- stream lifecycle: push and reset individual streams ------------------------ */
+/* Clients connect and drop, a network source is a packet late, a slot is reused: the calls below
+ * deliver ticks to, and reset, a subset of the streams.
+ *
+ * Own clock.  A stream's tick is the number of ticks delivered to it since creation or its last
+ * reset.  Its virtual clock (tick * tick_seconds), its re-entry timeout, ewk_event.tick and
+ * ewk_event.time are its own: stream s produces exactly what a one-stream engine produces when fed
+ * the same blocks in the same order, whatever the other streams were given in between.  An engine
+ * that is only ever pushed with ewk_push* is in lockstep and behaves as before.  The first
+ * ewk_push_streams* or ewk_reset_stream_list desynchronises it: from then on ewk_push* (a tick for
+ * every stream) also continues each stream's own clock, and ewk_normalize_events tests an event
+ * against its stream's tick.  ewk_reset_streams returns the engine to lockstep.  ewk_poll keeps its
+ * (tick, stream) order, each tick on its stream's clock.
+ *
+ * `streams` is always a host array, also with EWK_PUSH_DEVICE (only pcm is device memory then):
+ * 4 bytes per stream against 6.4 KB of audio.  It is validated on the host before anything is
+ * enqueued or changed: 1 <= n <= n_streams, every index in [0, n_streams), no index twice (two
+ * waves would run one stream) -- else EWK_EINVAL, naming the offending entry.  Any order; the
+ * array may die when the call returns, as pcm may. */
+/* Ticks for a subset of the streams.  Row i of pcm -- pcm[i*stride + t*tick_stride ...], input_block
+ * samples, strides in input samples as for ewk_push_many -- is tick t of stream streams[i].  Every
+ * listed stream gets the same n_ticks; gate launches are cut and scored as for ewk_push_many
+ * (single template, stream bank, EWK_SCORE_OVERLAP=1).  With an input rate set the history carried
+ * from push to push is that of streams[i]. */
+int ewk_push_streams(ewk_engine* e, const int32_t* streams, int32_t n, const float* pcm,
+                     int64_t stride, int64_t tick_stride, int32_t n_ticks, int32_t flags);
+int ewk_push_streams_pcm16(ewk_engine* e, const int32_t* streams, int32_t n, const int16_t* pcm,
+                           int64_t stride, int64_t tick_stride, int32_t n_ticks, int32_t flags);
+/* Streams streams[0..n) back to the state of a new engine; every other stream is untouched.
+ * Stream-ordered behind the pushes so far (and behind their scoring), no host synchronisation.
+ * After it each listed stream equals a stream of a freshly created engine: ring and block RMSs
+ * zero, initial threshold, tick 0, and with an input rate set an empty resampler history whose
+ * first `delay` outputs are zero again.  Events of the stream already queued keep their scores,
+ * but their samples are gone: ewk_read_segment / ewk_normalize_events on them is the caller's
+ * error (ewk_normalize_events reports an event from a tick its stream has not been pushed, or
+ * overwritten samples, where its tick test sees it).  Poll, then reset. */
+int ewk_reset_stream_list(ewk_engine* e, const int32_t* streams, int32_t n);
+/* Ticks delivered to each listed stream since creation or its last reset.  streams NULL: streams 0..n-1.
+ * Host bookkeeping only: no device access, no wait.  (The mirror costs nothing per ewk_push* on a
+ * lockstep engine -- one engine tick -- and O(n) per subset push or list reset: an engine base
+ * tick plus a per-stream delta, 8 bytes per stream, allocated when the engine desynchronises.) */
+int ewk_stream_ticks(ewk_engine* e, const int32_t* streams, int32_t n, int64_t* out);
+
 /* ---- level 1 + 2 against many references: the stream bank ---------------------- */
 /* From the next push on, every gated event of stream s is scored against the templates of word
  * stream_word[s] of the engine's bank (NULL: word 0 for every stream) instead of the single
@@ -295,6 +338,13 @@ int ewk_reset_streams(ewk_engine* e);
  * slot, 4 slots per stream), freed with the engine. */
 int ewk_stream_bank_enable(ewk_engine* e, const int32_t* stream_word);
 int ewk_stream_bank_disable(ewk_engine* e);   /* back to the single template; no-op when off */
+/* With the stream bank on: stream streams[i] listens for word words[i] from the next push on
+ * (a slot reused by a client with another word).  Host arrays, `streams` as for ewk_push_streams.
+ * Stream-ordered: the events of the pushes so far keep the word they were scored with, no wait.
+ * If the bank was enabled with stream_word NULL the per-stream array is created first, all zeros.
+ * EWK_EINVAL when the stream bank is off, for a stream out of range or listed twice, or a word
+ * outside [0, n_words); nothing changes then. */
+int ewk_stream_bank_assign(ewk_engine* e, const int32_t* streams, int32_t n, const int32_t* words);
 
 /* ---- either side of the path --------------------------------------- */
 /* Level-3 input: WakeWord._transcribe_audio's normalisation (wakeword.py:1019-1025)
