@@ -1,5 +1,6 @@
 """Host restatement of the input-rate resampler's streaming definition (include/ewk.h,
-ewk_set_input_rate), shared by tests/test_resample_design.py and tests/test_gpu_resample.py.
+ewk_set_input_rate) and of the kernel's launch geometry, shared by tests/test_resample_design.py
+and the resampler's GPU tests.
 
 The 16 kHz stream is the whole-signal resample y (easywakeword_amd.audio.resample) delayed by
 `delay` samples.  Output n uses c = (n - delay) * down + half, i = floor(c / up), p = c mod up:
@@ -18,6 +19,39 @@ def design_params(rate, out=OUT):
     half = 10 * max(up, down)
     J = 2 * half // up + 1
     return dict(up=up, down=down, half=half, J=J, H=J + 1, delay=-(-half // down))
+
+
+Q, MAX_THREADS, MAX_SPAN = 4, 1024, 12288      # kRsQ, kRsMaxThreads, kRsMaxSpan (ewk_internal.h)
+
+
+def launch_geometry(rate, out=OUT):
+    """The resample kernel's launch for `rate`, restated from resample_threads / resample_span /
+    rs_prepare: threads per workgroup, outputs per workgroup (tile), input samples a workgroup
+    stages (span), and whether the engine takes the rate at all (up and span within the limits)."""
+    p = design_params(rate, out)
+    up, down, J = p["up"], p["down"], p["J"]
+    threads = up if up > 256 else up * (256 // up)
+    tile = Q * threads
+    span = ((tile - 1) * down + up - 1) // up + J
+    return dict(threads=threads, tile=tile, span=span,
+                accepted=up <= MAX_THREADS and J + 1 <= MAX_SPAN and span <= MAX_SPAN)
+
+
+def one_shot_lengths(rate, out=OUT):
+    """[(n_in, n_out)] for a whole-signal resample whose outputs end just short of, on and just
+    past a workgroup's tile: n_out = ceil(n_in * up / down) of 1, tile - 1, tile, tile + 1 and
+    2 * tile + 3.  When upsampling not every n_out exists (4/3: 2, 3, 4, 6, ..): the nearest one
+    below and the nearest one above stand in for it."""
+    p = design_params(rate, out)
+    up, down = p["up"], p["down"]
+    tile = launch_geometry(rate, out)["tile"]
+    n_ins = set()
+    for target in (1, tile - 1, tile, tile + 1, 2 * tile + 3):
+        n_in = max(1, target * down // up)           # the longest input with n_out <= target
+        n_ins.add(n_in)
+        if -(-n_in * up // down) != target:
+            n_ins.add(n_in + 1)                      # the shortest with n_out > target
+    return [(n, -(-n * up // down)) for n in sorted(n_ins)]
 
 
 def host_taps(rate, out=OUT):

@@ -1,8 +1,8 @@
 """Subset pushes and list resets with an input rate set (ewk_set_input_rate): the resampler's
 history row and its "fresh" state (the first input_delay outputs are zero) belong to the stream.
 
-Four streams at 48 kHz float32 / 44.1 kHz PCM16.  Engine A is pushed in lockstep, engine B by a
-seeded subset schedule: events and rings are bit-identical.  Then streams 1 and 3 of B are reset
+Four streams at 48 kHz float32 / 44.1 kHz PCM16 / 12 kHz float32.  Engine A is pushed in
+lockstep, engine B by a seeded subset schedule: events and rings are bit-identical.  Then streams 1 and 3 of B are reset
 and fed what streams 0 and 2 heard from the start: they equal those streams of A, a fresh engine
 -- the first input_delay zeros included -- while streams 0 and 2 of B keep their state.
 """
@@ -33,7 +33,10 @@ def _input(rate, pcm16):
     return hi, ib
 
 
-@pytest.mark.parametrize("rate,pcm16", [(48000, False), (44100, True)], ids=["48k_f32", "44k1_pcm16"])
+# (12 kHz upsamples 4/3 with a negative phase offset c0 = -2: the floor-division branch of k_resample;
+# its band-limited streams give the oracle gate the same 8 events as the 48 kHz ones)
+@pytest.mark.parametrize("rate,pcm16", [(48000, False), (44100, True), (12000, False)],
+                         ids=["48k_f32", "44k1_pcm16", "12k_f32"])
 def test_subset_schedule_and_list_reset_at_input_rate(rate, pcm16):
     from easywakeword_amd import StreamEngine
     tm, ts = template_arrays(matcher_fixture()[0])

@@ -1,49 +1,19 @@
 """Input-rate resampler on the GPU: ewk_resample and the streaming push path at 48, 44.1 and
 8 kHz against easywakeword_amd.audio.resample (scipy's resample_poly, float64).
 
-Tolerance, every sample: |device - host| <= max(one float32 ulp of the host value, 2^-40 max|x|).
-Both sides accumulate at most 256 products in float64 (error < 2^-43 max|x|) and round once to
-float32, so they can differ only where the float64 sums straddle a rounding boundary, and then
-by one ulp; the absolute term covers outputs that cancel to near zero.  The count of samples that
-are not bit-equal is printed (expected: about none)."""
-import ctypes as C
-
+The tolerance (one float32 ulp) and its argument are in resample_gpu_util.py; the other rates
+and launch geometries are in test_gpu_resample_rates.py."""
 import numpy as np
 import pytest
 
 import synth
 from golden_io import matcher_fixture, template_arrays
-from resample_ref import OUT, delayed_resample, design_params
+from resample_gpu_util import BLOCK, assert_close, in_block_of, push_sequence, signal, stream_data
+from resample_ref import OUT, design_params
 
 pytestmark = pytest.mark.gpu
 
 RATES = (48000, 44100, 8000)
-BLOCK = 1600
-
-
-def in_block_of(rate):
-    p = design_params(rate)
-    return BLOCK * p["down"] // p["up"]
-
-
-def assert_close(dev, host, x_max, what):
-    dev, host = np.asarray(dev, np.float32), np.asarray(host, np.float32)
-    assert dev.shape == host.shape, (what, dev.shape, host.shape)
-    if dev.size == 0:
-        return 0
-    tol = np.maximum(np.spacing(np.abs(host)).astype(np.float64), 2.0 ** -40 * float(x_max))
-    err = np.abs(dev.astype(np.float64) - host.astype(np.float64))
-    unequal = int(np.count_nonzero(dev != host))
-    print(f"{what}: {dev.size} samples, {unequal} not bit-equal, max err {float(err.max()):.3e}")
-    bad = np.flatnonzero(~(err <= tol))
-    assert bad.size == 0, (what, bad[:8], dev[bad[:8]], host[bad[:8]])
-    return unequal
-
-
-def signal(kind, n, seed):
-    if kind == "noise":
-        return (0.3 * np.random.default_rng(seed).standard_normal(n)).astype(np.float32)
-    return np.where((np.arange(n) // 37) % 2 == 0, 1.0, -1.0).astype(np.float32)   # full-scale square wave
 
 
 @pytest.fixture(scope="module")
@@ -82,68 +52,24 @@ def test_one_shot_equals_host_resample(scorer, rate, kind):
         scorer.resample(np.zeros(8, np.float32), 0)
 
 
-def _push_sequence(eng, data, rate, pcm16):
-    """One push, one push_many of 3 ticks with tick_stride != in_block, two pushes; streams
-    stride > in_block apart.  data: [3][6 * in_block].  After each call read_last of the ticks just
-    pushed is checked against the delayed host resample of everything pushed so far; returns
-    every read_last, concatenated."""
-    from easywakeword_amd import _lib
-    lib = eng._lib
-    ib = in_block_of(rate)
-    n_s = data.shape[0]
-    dt = np.int16 if pcm16 else np.float32
-    x = data if not pcm16 else data.astype(np.float32) / np.float32(32768.0)
-    want = [delayed_resample(x[s], rate, 6 * BLOCK) for s in range(n_s)]
-    x_max = float(np.max(np.abs(x)))
-    out = []
-    done = 0
-    for nt in (1, 3, 1, 1):
-        tick_stride = ib + 5
-        stride = nt * tick_stride + 11
-        buf = np.full(n_s * stride, 9 if pcm16 else 9.0, dt)       # the gaps must not be read
-        for s in range(n_s):
-            for t in range(nt):
-                buf[s * stride + t * tick_stride: s * stride + t * tick_stride + ib] = \
-                    data[s, (done + t) * ib:(done + t + 1) * ib]
-        ptr = buf.ctypes.data_as(C.c_void_p)
-        if nt == 1:
-            fn = lib.ewk_push_pcm16 if pcm16 else lib.ewk_push
-            _lib.check(fn(eng.handle, ptr, stride, 0))
-        else:
-            fn = lib.ewk_push_many_pcm16 if pcm16 else lib.ewk_push_many
-            _lib.check(fn(eng.handle, ptr, stride, tick_stride, nt, 0))
-        done += nt
-        for s in range(n_s):
-            got = eng.read_last(s, nt * BLOCK)
-            assert_close(got, want[s][(done - nt) * BLOCK: done * BLOCK], x_max,
-                         f"{rate} Hz {'pcm16' if pcm16 else 'f32'} stream {s} ticks {done - nt}..{done}")
-            out.append(got)
-    d = design_params(rate)["delay"]
-    assert all(np.all(w[:d] == 0) for w in want)
-    return np.concatenate(out)
-
-
 @pytest.mark.parametrize("pcm16", [False, True], ids=["f32", "pcm16"])
 @pytest.mark.parametrize("rate", RATES)
 def test_streaming_equals_delayed_host_resample(rate, pcm16):
     from easywakeword_amd import StreamEngine
     ib = in_block_of(rate)
     p = design_params(rate)
-    rng = [np.random.default_rng(1000 * rate + s) for s in range(3)]
-    data = np.stack([(0.25 * r.standard_normal(6 * ib)).astype(np.float32) for r in rng])
-    if pcm16:
-        data = np.clip(np.round(data * 32768.0), -32768, 32767).astype(np.int16)
+    data = stream_data(rate, 6, pcm16)
     eng = StreamEngine(3)
     assert (eng.input_rate, eng.input_block, eng.input_delay) == (OUT, BLOCK, 0)
     eng.set_input_rate(rate)
     assert (eng.input_rate, eng.input_block, eng.input_delay) == (rate, ib, p["delay"])
-    first = _push_sequence(eng, data, rate, pcm16)
+    first = push_sequence(eng, data, rate, pcm16)
     eng.reset()                                # the history is cleared: the same output again
-    again = _push_sequence(eng, data, rate, pcm16)
+    again = push_sequence(eng, data, rate, pcm16)
     assert np.array_equal(first, again)
     eng.set_input_rate(0)                      # back to 16 kHz pushes
     assert (eng.input_rate, eng.input_block, eng.input_delay) == (OUT, BLOCK, 0)
-    blk = (0.1 * rng[0].standard_normal((3, BLOCK))).astype(np.float32)
+    blk = (0.1 * np.random.default_rng(rate).standard_normal((3, BLOCK))).astype(np.float32)
     eng.push(blk)
     for s in range(3):
         assert np.array_equal(eng.read_last(s, BLOCK), blk[s])

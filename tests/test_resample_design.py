@@ -7,7 +7,7 @@ from math import gcd
 import numpy as np
 import pytest
 
-from resample_ref import design_params, stream_resample_ref
+from resample_ref import design_params, launch_geometry, one_shot_lengths, stream_resample_ref
 
 RATES = (48000, 44100, 8000, 32000, 22050, 96000)
 OUT = 16000
@@ -66,17 +66,26 @@ def test_new_symbols_are_exported():
     assert lib.ewk_abi_version() == 4
 
 
-@pytest.mark.parametrize("rate", RATES)
-def test_streaming_definition_equals_delayed_whole_signal_resample(rate):
-    """Block by block, each tick from its own in_block samples and the H = J + 1 samples before
-    them (sequential float64 sums in ascending input order, one rounding to float32), the 16 kHz
-    stream is concat(zeros(delay), audio.resample(x)) bit for bit: pins delay and look-ahead."""
+# the streaming definition also at the rates whose phase offset c0 = half - delay * down is
+# negative (upsampling, `down` not dividing 10 * up), at 176.4 kHz (J = 221) and at rates whose
+# tick is shorter than the history (1 kHz with block 320: 20 samples against H = 22)
+STREAM_RATES = RATES + (24000, 12000, 12800, 9600, 176400, 1000, 2000)
+NEGATIVE_C0 = {12000: -2, 12800: -2, 9600: -1}
+
+
+def _check_streaming_definition(rate, block):
     from easywakeword_amd.audio import resample
     _, taps, _, up, down = design(rate)
     p = design_params(rate)
     assert (p["up"], p["down"]) == (up, down)
-    block, ticks = 1600, 2
+    c0 = p["half"] - p["delay"] * down
+    assert -down < c0 <= 0
+    if rate in NEGATIVE_C0:
+        assert c0 == NEGATIVE_C0[rate] < 0
+    ticks = 13 if rate in (1000, 2000) else 2
     in_block = block * down // up
+    if (rate, block) == (1000, 320):
+        assert in_block < p["H"]              # a tick's history reaches into the tick before the last
     rng = np.random.default_rng(rate)
     x = (0.5 * rng.standard_normal(ticks * in_block)).astype(np.float32)
     got = stream_resample_ref(x, rate, block, taps=taps)
@@ -86,3 +95,40 @@ def test_streaming_definition_equals_delayed_whole_signal_resample(rate):
     bad = np.flatnonzero(got != want)
     assert bad.size == 0, (rate, bad[:8], got[bad[:8]], want[bad[:8]])
     assert np.all(got[: p["delay"]] == 0)
+
+
+@pytest.mark.parametrize("rate", RATES)
+def test_streaming_definition_equals_delayed_whole_signal_resample(rate):
+    """Block by block, each tick from its own in_block samples and the H = J + 1 samples before
+    them (sequential float64 sums in ascending input order, one rounding to float32), the 16 kHz
+    stream is concat(zeros(delay), audio.resample(x)) bit for bit: pins delay and look-ahead."""
+    _check_streaming_definition(rate, 1600)
+
+
+@pytest.mark.parametrize("rate,block", [(r, b) for b in (1600, 320) for r in STREAM_RATES
+                                        if not (b == 1600 and r in RATES)])
+def test_streaming_definition_at_more_rates_and_blocks(rate, block):
+    """The same at 320-sample ticks and at the further rates of STREAM_RATES (13 ticks at 1 and 2 kHz)."""
+    _check_streaming_definition(rate, block)
+
+
+def test_launch_geometry_table():
+    """The workgroup size and staged span of each rate the GPU tests run (resample_threads,
+    resample_span), and the rates on the far side of the limits."""
+    table = {22050: (320, 1791), 12800: (255, 837), 176400: (240, 10794), 176000: (256, 11474),
+             11025: (640, 1785), 16016: (1000, 4024), 96000: (256, 6259), 48000: (256, 3130), 8000: (256, 533)}
+    for rate, (threads, span) in table.items():
+        g = launch_geometry(rate)
+        assert (g["threads"], g["span"], g["accepted"]) == (threads, span, True), (rate, g)
+        assert g["tile"] == 4 * threads and threads % design_params(rate)["up"] == 0
+        lengths = one_shot_lengths(rate)
+        outs = [n_out for _, n_out in lengths]
+        assert outs == sorted(set(outs)) and all(n_in >= 1 for n_in, _ in lengths)
+        assert g["tile"] in outs and outs[0] <= 2 and outs[-1] >= 2 * g["tile"] + 3
+        assert any(o < g["tile"] for o in outs[1:]) and any(g["tile"] < o < 2 * g["tile"] for o in outs)
+        if design_params(rate)["down"] >= design_params(rate)["up"]:      # downsampling reaches every n_out
+            assert outs == [1, g["tile"] - 1, g["tile"], g["tile"] + 1, 2 * g["tile"] + 3]
+    g = launch_geometry(192000)
+    assert (g["span"], g["accepted"]) == (12517, False)
+    assert design_params(16001)["up"] == 16000 and not launch_geometry(16001)["accepted"]
+    assert design_params(176400)["J"] == 221 and design_params(96000)["J"] == 121
