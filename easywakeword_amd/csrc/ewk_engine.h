@@ -1,0 +1,254 @@
+// ewk_engine.h -- the engine behind the C ABI (include/ewk.h): its state, and the helpers its
+// sources share.  Internal: only ewk_engine.cpp and ewk_engine_{score,stream,resample}.cpp include it.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "ewk_gate.h"
+#include "ewk_internal.h"
+
+namespace ewk {
+
+// Sets the calling thread's ewk_last_error string and returns `code`.
+int fail(int code, const std::string& msg);
+
+#define HIP_TRY(expr)                                                                          \
+    do {                                                                                       \
+        hipError_t _e = (expr);                                                                \
+        if (_e != hipSuccess)                                                                  \
+            return fail(EWK_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e));          \
+    } while (0)
+
+// Device memory that grows and is freed with its owner (callers synchronize before a
+// temporary goes out of scope).
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;   // elements
+    unsigned flags = 0;   // hipExtMallocWithFlags flags (0: hipMalloc)
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    hipError_t reserve(size_t n) {
+        if (n <= cap) return hipSuccess;
+        release();
+        size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
+        hipError_t e = flags ? hipExtMallocWithFlags((void**)&p, bytes, flags) : hipMalloc(&p, bytes);
+        if (e == hipSuccess) cap = n;
+        return e;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+};
+
+constexpr int kWorkInts = 32;          // ewk_engine::d_work
+constexpr int32_t kPollChunk = 1024;   // events copied speculatively with the counters
+constexpr size_t kPollRegion = 16 + (size_t)kPollChunk * sizeof(ewk_event);   // per bank: counters + chunk
+constexpr const char* kNoBank = "No reference word set. Call set_bank() first.";
+
+}  // namespace ewk
+
+struct ewk_engine {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    ewk_config cfg{};
+    int32_t n_streams = 0;
+    int64_t ring_len = 0;           // the reference ring (buffer_seconds * sample_rate)
+    int64_t sring_len = 0;          // samples stored per stream (ring_len, or cfg.ring_samples)
+    int32_t n_blocks = 0;
+    int64_t n_last = 0;
+
+    ewk::Tables* d_tab = nullptr;
+    ewk::Tables64* d_tab64 = nullptr;
+    float* d_tmpl = nullptr;
+    float h_tmpl[2 * ewk::NMFCC];
+    float uu_m32 = 0.f, uu_s32 = 0.f;   // numpy float32 dot of the template with itself
+    bool has_tmpl = false;
+
+    // fp64 re-score (ewk_rescore.h): slots of listed segments and the chunk part pool, shared
+    // by linear and ring launches (which never run concurrently: join_scoring)
+    ewk::DevBuf<ewk::RsSlot> rs_slots;
+    ewk::DevBuf<int32_t> rs_serial;      // serial slots of a launch
+    ewk::DevBuf<ewk::RsPart> rs_parts;   // uncached (ScoreArgs::rs_ctl)
+    int32_t rs_cap = 0;             // slots
+    int32_t rs_part_cap = 0;        // part records (a slot that finds the pool full runs serially)
+    // [0] linear work, [1] ring work, [4..5] event-count snapshots, [16..23] ring re-score
+    // counters (ScoreArgs::rs_ctl), [24..31] linear re-score counters
+    int32_t* d_work = nullptr;
+    int32_t* d_compact = nullptr;   // ewk_compact_positives block counts / offsets
+    int32_t compact_cap = 0;        // ... in blocks
+    ewk::DevBuf<int32_t> order;     // linear batches: longest-first work order (k_lpt_order)
+
+    // host-API staging
+    ewk::DevBuf<float> pcm;
+    ewk::DevBuf<int64_t> offsets;
+    ewk::DevBuf<int32_t> lengths;
+    ewk::DevBuf<float> mean, stdv;
+    ewk::DevBuf<double> score;
+    ewk::DevBuf<uint8_t> match;
+    ewk::DevBuf<double> mean64, std64;
+
+    // template bank (ewk_bank.hip): host copy as set, device copy value-major per word
+    std::vector<float> bank_mean, bank_std;   // [K][20]
+    std::vector<int32_t> bank_first;          // [n_words + 1]; empty: no bank
+    std::vector<double> bank_thr;             // [n_words]
+    bool bank_thr_follow = false;             // thresholds follow cfg.similarity_threshold
+    int32_t bank_max_word = 0;
+    ewk::DevBuf<float> d_bank;                // [K][kBankRow] (BankArgs::bank)
+    ewk::DevBuf<int32_t> d_bank_first;
+    ewk::DevBuf<double> d_bank_thr;
+    ewk::DevBuf<int32_t> bk_cnt, bk_seg, bk_len;   // the fp64 list of a bank scoring call
+    ewk::DevBuf<int64_t> bk_off;
+    ewk::DevBuf<int32_t> bk_word;             // host-call staging
+    ewk::DevBuf<ewk_bank_result> bk_out;
+    ewk::DevBuf<double> bk_scores;
+    // stream bank (ewk_stream_bank_enable): gated events are scored against the bank.  Per event
+    // slot (one set for both event banks: scoring passes are serialised on their stream) the
+    // float32 statistics and theta_s of the ring scorer, the fp64 statistics of the re-score, and
+    // the list of the events a pass re-scores (BankEvArgs::ev_list); allocated at the first enable.
+    bool sbank_on = false;
+    bool sbank_words = false;                 // sb_word holds a word per stream (else: word 0)
+    ewk::DevBuf<int32_t> sb_word;             // [n_streams]
+    ewk::DevBuf<float> sb_mean, sb_std, sb_theta;  // [ev_cap][20], [ev_cap][20], [ev_cap]
+    ewk::DevBuf<double> sb_mean64, sb_std64;  // [ev_cap][20]
+    ewk::DevBuf<int32_t> sb_list;             // [kEvListHdr + ev_cap]
+
+    // streaming
+    void* d_ring = nullptr;         // float32 or int16 samples (cfg.ring_format)
+    size_t ring_es = sizeof(float); // bytes per ring sample
+    float* ring_f32() const { return ring_es == sizeof(float) ? static_cast<float*>(d_ring) : nullptr; }
+    int16_t* ring_i16() const { return ring_es == sizeof(int16_t) ? static_cast<int16_t*>(d_ring) : nullptr; }
+    double* d_brms = nullptr;
+    double* d_sorted = nullptr;     // [streams][2][n_blocks] sorted block RMS (double-buffered)
+    ewk::PwTree* d_trees = nullptr; // numpy pairwise-sum trees for the block and the last 0.1 s
+    ewk::GateStream* d_st = nullptr;
+    // Two event banks (ev_cap events + 4 counters each: [0] count, [1] dropped,
+    // [2] scored watermark): pushes append to `bank`; ewk_poll_lagged drains the
+    // other bank while the GPU still works on this one.  The counters only grow (wrapping
+    // uint32): a drained bank is re-armed by moving its epoch base to the count the host
+    // read -- event i of an epoch is at slot count - base -- so no fill launch per tick.
+    ewk_event* d_events = nullptr;   // [2][ev_cap]
+    int32_t* d_evc = nullptr;        // [2][4]
+    uint32_t ev_base0[2] = {0, 0};   // per bank: count at the start of the current epoch
+    uint32_t drop_base0[2] = {0, 0}; // per bank: dropped count at the start of the epoch
+    int32_t ev_cap = 0;
+    int bank = 0;
+    bool bank_used[2] = {false, false};
+    hipEvent_t bank_done[2] = {nullptr, nullptr};   // recorded after the last push into a bank
+    hipStream_t cstream = nullptr;                  // D2H copies of drained banks
+    // Ring-mode scoring of tick t runs on sstream concurrently with the gate of tick t+1
+    // on `stream` (the gate only overwrites ring samples older than any scorable segment;
+    // see `overlap`).  At most one scoring pass is in flight beside a gate.
+    hipStream_t sstream = nullptr;
+    hipEvent_t gate_evt[2] = {nullptr, nullptr};
+    hipEvent_t score_evt[2] = {nullptr, nullptr};
+    bool score_live[2] = {false, false};
+    hipEvent_t score_tail = nullptr;                // the latest recorded score_evt
+    int64_t push_seq = 0;
+    bool overlap = false;
+    int32_t ticks_per_launch = 32;                  // gate launch length (segments must outlive it in the ring)
+    ewk_event* ev_bank(int b) { return d_events + (size_t)b * ev_cap; }
+    int32_t* evc_bank(int b) { return d_evc + 4 * b; }
+    ewk::DevBuf<float> push_stage;
+    float* h_stage = nullptr;       // pinned host staging for ewk_push / ewk_push_many
+    unsigned char* h_poll = nullptr;   // pinned: event counters + the first kPollChunk events
+    unsigned char* d_poll = nullptr;   // h_poll's device address (k_bank_mirror writes it)
+    // mirror[b]: h_poll's region b holds bank b as of bank_done[b], written by k_bank_mirror
+    // after the push's last scoring pass (same stream) -- the poll needs no copies
+    bool mirror[2] = {false, false};
+    size_t h_stage_cap = 0;
+    hipEvent_t h_stage_free = nullptr;   // recorded after the last DMA out of h_stage
+    int64_t tick = 0;
+    // Stream lifecycle (ewk_push_streams / ewk_reset_stream_list).  A lockstep engine has one clock,
+    // `tick`.  The first subset push or list reset desynchronises it: stream s has then had
+    // tick + tick_delta[s] ticks (the host mirror of GateStream::tick; full pushes still only
+    // advance `tick`) and the gate runs every stream on its own clock.  ewk_reset_streams returns
+    // the engine to lockstep.  seen / seen_epoch: the duplicate test of an index list, O(n) per call.
+    bool desync = false;
+    std::vector<int64_t> tick_delta;   // [n_streams] once desynchronised
+    std::vector<uint32_t> seen;        // [n_streams]: the epoch of the call that last listed the stream
+    uint32_t seen_epoch = 0;
+    int32_t* h_ids = nullptr;          // pinned [2 * n_streams]: an index list (and its words) on the way to d_ids
+    ewk::DevBuf<int32_t> d_ids;        // [2 * n_streams]
+    hipEvent_t h_ids_free = nullptr;   // recorded after the last DMA out of h_ids
+    int64_t stream_tick(int32_t s) const { return tick + (desync ? tick_delta[s] : 0); }
+    int32_t gate_stage = 0;
+    int32_t gate_val_len = 0;       // per-wave LDS doubles of the gate (tree values, sort scratch)
+
+    // input-rate resampler (ewk_resample.hip).  rs_in: the filter of ewk_set_input_rate, with the
+    // per-stream history ([n_streams][H] float32: the last H input samples) and the resampled
+    // ticks the gate reads ([n_streams][n_ticks * block], grown to the longest push so far);
+    // rs_one: the filter of the latest ewk_resample call.
+    struct RsFilter {
+        int32_t rate = 0, up = 1, down = 1, half = 0, J = 0, H = 0, threads = 0, span = 0;
+        int64_t c0 = 0;             // ResampleArgs::c0
+        ewk::DevBuf<double> taps;   // [J][up]
+    };
+    RsFilter rs_in, rs_one;
+    bool rs_on = false;
+    bool rs_fresh = true;   // no push since the history was cleared: the first `delay` outputs are zero
+    int32_t rs_in_block = 0, rs_delay = 0;
+    ewk::DevBuf<float> rs_hist, rs_out;
+    // the same per stream ([n_streams], device), in place of rs_fresh from the first subset push or
+    // list reset with a rate set: set where a stream's history was cleared, cleared by its next push
+    ewk::DevBuf<uint8_t> rs_flags;
+
+    // measurement: (start, stop) event pairs per kernel family
+    bool prof = false;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[4];
+    std::vector<hipEvent_t> ev_pool;
+};
+
+namespace ewk {
+
+hipEvent_t pool_event(ewk_engine* e);   // from ev_pool, or a new one (nullptr: none to be had)
+
+// RAII bracket: records start/stop events around one launch when profiling.
+struct ProfScope {
+    ewk_engine* e;
+    int kind;
+    hipStream_t s;
+    hipEvent_t a = nullptr, b = nullptr;
+    ProfScope(ewk_engine* e_, int kind_, hipStream_t s_) : e(e_), kind(kind_), s(s_) {
+        if (!e->prof) return;
+        a = pool_event(e);
+        b = pool_event(e);
+        if (a) (void)hipEventRecord(a, s);
+    }
+    ~ProfScope() {
+        if (!e->prof || !a || !b) return;
+        (void)hipEventRecord(b, s);
+        e->ev[kind].push_back({a, b});
+    }
+};
+
+// Where the tick samples of a push are now: stream (row) r, tick t at p + r * stride + t * tick_stride.
+struct TickSrc {
+    const void* p;
+    bool pcm16;   // int16 PCM, else float32
+    int64_t stride, tick_stride;
+};
+
+// ewk_engine.cpp
+hipError_t join_scoring(ewk_engine* e, hipStream_t s);
+hipError_t reserve_rescore(ewk_engine* e, int32_t n_seg);
+// ewk_engine_score.cpp
+ScoreArgs base_args(ewk_engine* e);
+BankArgs bank_args(ewk_engine* e);
+int bank_follow_threshold(ewk_engine* e, hipStream_t s);
+enum WordOf { kOfSegment, kOfStream };   // "word index W of {segment|stream} I is outside [0, N)"
+int fail_word_index(int32_t word, WordOf of, int32_t i, int32_t n_words);
+// ewk_engine_resample.cpp: a push's resample stage -- every tick at *src into rs_out (float32 16 kHz
+// blocks, where *src then points), the history saved for the next push; d_list: ResampleArgs::ids
+int resample_ticks(ewk_engine* e, TickSrc* src, int32_t rows, int32_t n_ticks, const int32_t* d_list, hipStream_t s);
+
+}  // namespace ewk

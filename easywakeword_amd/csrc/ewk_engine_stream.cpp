@@ -1,0 +1,720 @@
+// ewk_engine_stream.cpp -- the C ABI's streaming side (levels 1 + 2): pushes and the scoring
+// passes behind them, stream index lists and the stream lifecycle, the stream bank, polls and
+// ring reads.
+#include "ewk_engine.h"
+
+using namespace ewk;
+
+static void zero_event_state(ewk_engine* e) {
+    if (e->d_evc) (void)hipMemsetAsync(e->d_evc, 0, 8 * sizeof(int32_t), e->stream);
+    e->ev_base0[0] = e->ev_base0[1] = 0;
+    e->drop_base0[0] = e->drop_base0[1] = 0;
+    e->bank_used[0] = e->bank_used[1] = false;
+    e->mirror[0] = e->mirror[1] = false;
+}
+
+static hipError_t ensure_poll_region(ewk_engine* e) {
+    if (e->h_poll && e->d_poll) return hipSuccess;
+    if (!e->h_poll) {
+        hipError_t err = hipHostMalloc((void**)&e->h_poll, 2 * kPollRegion, hipHostMallocDefault);
+        if (err != hipSuccess) { e->h_poll = nullptr; return err; }
+    }
+    hipError_t err = hipHostGetDevicePointer((void**)&e->d_poll, e->h_poll, 0);
+    if (err != hipSuccess) {   // never leave a host region without its device alias (the mirror writes through it)
+        (void)hipHostFree(e->h_poll);
+        e->h_poll = nullptr;
+        e->d_poll = nullptr;
+    }
+    return err;
+}
+
+int ewk_reset_streams(ewk_engine* e) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (e->n_streams <= 0) return EWK_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    HIP_TRY(join_scoring(e, s));
+#ifndef EWK_RING_MEMSET
+    HIP_TRY(launch_ring_zero(e->d_ring, (size_t)e->n_streams * e->sring_len * e->ring_es, s));
+#else   // (the round-6 fill, kept for the A/B of scripts/gpu_miss_prefix.sh)
+    HIP_TRY(hipMemsetAsync(e->d_ring, 0, (size_t)e->n_streams * e->sring_len * e->ring_es, s));
+#endif
+    HIP_TRY(hipMemsetAsync(e->d_brms, 0, (size_t)e->n_streams * std::max(1, e->n_blocks) * sizeof(double), s));
+    std::vector<GateStream> st(e->n_streams);
+    for (auto& x : st) {
+        memset(&x, 0, sizeof(x));
+        x.threshold = e->cfg.initial_threshold;
+        x.last_silent = 1;
+    }
+    HIP_TRY(hipMemcpyAsync(e->d_st, st.data(), st.size() * sizeof(GateStream), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(e->d_work, 0, kWorkInts * sizeof(int32_t), s));
+    // (a stream bank stays enabled; its list of events to re-score starts empty)
+    if (e->sb_list.p) HIP_TRY(hipMemsetAsync(e->sb_list.p, 0, kEvListHdr * sizeof(int32_t), s));
+    // (an input rate stays set; the resampler's history starts from silence again)
+    if (e->rs_hist.p) HIP_TRY(hipMemsetAsync(e->rs_hist.p, 0, e->rs_hist.cap * sizeof(float), s));
+    if (e->rs_flags.p) HIP_TRY(hipMemsetAsync(e->rs_flags.p, 1, e->rs_flags.cap, s));
+    e->rs_fresh = true;
+    zero_event_state(e);
+    HIP_TRY(hipStreamSynchronize(s));
+    e->tick = 0;
+    e->desync = false;   // one clock again
+    std::vector<int64_t>().swap(e->tick_delta);
+    return EWK_OK;
+}
+
+// ---- stream lifecycle: index lists --------------------------------------------------
+// An index list as every call that takes one requires it: 1 <= n <= n_streams, every entry a
+// stream, none twice (two waves would run one stream).  Host only; changes nothing but `seen`.
+static int fail_stream_index(ewk_engine* e, int32_t i, int32_t s) {
+    return fail(EWK_EINVAL, "streams[" + std::to_string(i) + "] = " + std::to_string(s) + " is outside [0, " +
+                                std::to_string(e->n_streams) + ")");
+}
+
+static int check_stream_list(ewk_engine* e, const int32_t* streams, int32_t n) {
+    if (!streams) return fail(EWK_EINVAL, "streams is NULL");
+    if (n < 1 || n > e->n_streams)
+        return fail(EWK_EINVAL, "a stream list holds 1.." + std::to_string(e->n_streams) + " streams, got " +
+                                    std::to_string(n));
+    if (e->seen.empty()) e->seen.assign((size_t)e->n_streams, 0);
+    if (++e->seen_epoch == 0) {   // (wrapped: forget every earlier call)
+        std::fill(e->seen.begin(), e->seen.end(), 0);
+        e->seen_epoch = 1;
+    }
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t s = streams[i];
+        if (s < 0 || s >= e->n_streams) return fail_stream_index(e, i, s);
+        if (e->seen[s] == e->seen_epoch)
+            return fail(EWK_EINVAL, "streams[" + std::to_string(i) + "]: stream " + std::to_string(s) +
+                                        " is listed twice");
+        e->seen[s] = e->seen_epoch;
+    }
+    return EWK_OK;
+}
+
+// The list (and `vals`, one per entry, when given) to the device on s through pinned staging:
+// the caller's arrays may die on return.  *d_list / *d_vals: where kernels enqueued on s after
+// this call find them, until the next call.
+static int stage_stream_list(ewk_engine* e, const int32_t* streams, const int32_t* vals, int32_t n, hipStream_t s,
+                             const int32_t** d_list, const int32_t** d_vals) {
+    const size_t cap = 2 * (size_t)e->n_streams;
+    if (!e->h_ids) {
+        HIP_TRY(hipHostMalloc((void**)&e->h_ids, cap * sizeof(int32_t), hipHostMallocDefault));
+        HIP_TRY(hipEventCreateWithFlags(&e->h_ids_free, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(e->h_ids_free, s));
+    }
+    HIP_TRY(e->d_ids.reserve(cap));
+    HIP_TRY(hipEventSynchronize(e->h_ids_free));   // the previous list has left the staging
+    memcpy(e->h_ids, streams, (size_t)n * sizeof(int32_t));
+    if (vals) memcpy(e->h_ids + e->n_streams, vals, (size_t)n * sizeof(int32_t));
+    HIP_TRY(hipMemcpyAsync(e->d_ids.p, e->h_ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (vals)
+        HIP_TRY(hipMemcpyAsync(e->d_ids.p + e->n_streams, e->h_ids + e->n_streams, (size_t)n * sizeof(int32_t),
+                               hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(e->h_ids_free, s));
+    *d_list = e->d_ids.p;
+    if (d_vals) *d_vals = e->d_ids.p + e->n_streams;
+    return EWK_OK;
+}
+
+// First subset push or list reset: every stream gets a clock of its own.  With a rate set, also
+// the per-stream fresh flags, from the engine-wide one.
+static int desynchronise(ewk_engine* e, hipStream_t s) {
+    if (!e->desync) {
+        e->tick_delta.assign((size_t)e->n_streams, 0);
+        e->desync = true;
+    }
+    if (e->rs_on && !e->rs_flags.p) {
+        HIP_TRY(e->rs_flags.reserve((size_t)e->n_streams));
+        HIP_TRY(hipMemsetAsync(e->rs_flags.p, e->rs_fresh ? 1 : 0, e->rs_flags.cap, s));
+    }
+    return EWK_OK;
+}
+
+// ---- scoring passes (ring mode) -----------------------------------------------------
+// The current bank's events [ev_base, *n_events) as segments of the rings; n_events is the live
+// counter (same stream as the gate) or a snapshot of it taken after the gate.  The re-score
+// launch (after the scorer) re-scores the listed segments in fp64 and its last workgroup out
+// advances the watermark.
+static ScoreArgs ring_args(ewk_engine* e, const int32_t* n_events) {
+    ScoreArgs a = base_args(e);
+    a.pcm = e->ring_f32();
+    a.pcm16 = e->ring_i16();
+    a.ring_len = e->sring_len;
+    a.events = e->ev_bank(e->bank);
+    a.n_events = n_events;
+    a.ev_base = e->evc_bank(e->bank) + 2;
+    a.ev_base0 = e->ev_base0[e->bank];
+    a.n_seg = e->ev_cap;
+    a.work = e->d_work + 1;            // ring-mode counters (zeroed at create, re-armed by the tick end)
+    a.rs_ctl = e->d_work + 16;
+    a.adv_ev_base = e->evc_bank(e->bank) + 2;
+    a.evc = e->evc_bank(e->bank);
+    return a;
+}
+
+// Workgroups of the stream bank's event passes: the waves stride over the pending events, so
+// the grid follows the engine's size (an empty tick only pays for reading the counters).
+static int32_t stream_bank_grid(const ewk_engine* e) {
+    return std::min(1024, std::max(8, (e->n_streams + 255) / 256));
+}
+
+// A scoring pass with the stream bank enabled, all on ss, every hand-off a kernel boundary:
+//   1 the ring scorer without a template: float32 statistics and theta_s by event slot
+//   2 k_bank_events<float>: every pending event against its stream's word; lists the events the
+//     float32 statistics cannot decide (re-score slots + sb_list)
+//   3 the re-score launch: fp64 statistics of the listed events; ends the tick (counters,
+//     watermark) without the poll mirror -- pass 4 still changes events
+//   4 k_bank_events<double>: the listed events again from the fp64 statistics
+// push_impl writes the poll mirror behind the push's last pass.
+static int score_pending_bank(ewk_engine* e, hipStream_t ss, const int32_t* n_events) {
+    {
+        int rc = bank_follow_threshold(e, ss);
+        if (rc) return rc;
+    }
+    ScoreArgs a = ring_args(e, n_events);
+    a.has_template = 0;
+    a.rs_slots = e->rs_slots.p;
+    a.out_mean = e->sb_mean.p;   // statistics by event slot
+    a.out_std = e->sb_std.p;
+    a.out_theta = e->sb_theta.p;
+    a.out_mean64 = e->sb_mean64.p;
+    a.out_std64 = e->sb_std64.p;
+    BankArgs b = bank_args(e);
+    BankEvArgs x;
+    x.stream_word = e->sbank_words ? e->sb_word.p : nullptr;
+    x.ev_list = e->sb_list.p;
+    x.grid = stream_bank_grid(e);
+    {
+        ProfScope ps(e, 0, ss);
+        HIP_TRY(launch_score_f32(e->d_tab, a, e->n_streams >= kRingWaveStreams ? 2 : 1, ss));
+    }
+    b.mean = e->sb_mean.p;
+    b.stdv = e->sb_std.p;
+    HIP_TRY(launch_bank_events(b, a, x, ss));
+    {
+        ProfScope ps(e, 1, ss);
+        HIP_TRY(launch_rescore_ring(a, ss));
+    }
+    b.mean = e->sb_mean64.p;
+    b.stdv = e->sb_std64.p;
+    HIP_TRY(launch_bank_events_rescore(b, a, x, ss));
+    return EWK_OK;
+}
+
+// Score the events queued since the last scoring pass on ss, then advance the watermark.
+static int score_pending(ewk_engine* e, hipStream_t ss, const int32_t* n_events) {
+    if (e->sbank_on) return score_pending_bank(e, ss, n_events);   // (needs no single template)
+    if (!e->has_tmpl) return EWK_OK;   // events keep NaN scores until a template exists
+    ScoreArgs a = ring_args(e, n_events);
+    HIP_TRY(ensure_poll_region(e));    // the re-score launch's last workgroup out writes the poll mirror
+    a.mirror = e->d_poll + e->bank * kPollRegion;
+    a.mirror_chunk = std::min<int32_t>(kPollChunk, e->ev_cap);
+    {
+        ProfScope ps(e, 0, ss);
+        HIP_TRY(launch_score_f32(e->d_tab, a, e->n_streams >= kRingWaveStreams ? 2 : 1, ss));
+    }
+    {
+        ProfScope ps(e, 1, ss);
+        HIP_TRY(launch_rescore_ring(a, ss));
+    }
+    return EWK_OK;
+}
+
+int ewk_stream_bank_enable(ewk_engine* e, const int32_t* stream_word) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (e->n_streams <= 0) return fail(EWK_EINVAL, "engine has no streams");
+    if (e->bank_first.empty()) return fail(EWK_ENOTEMPLATE, kNoBank);
+    const int32_t n_words = (int32_t)e->bank_first.size() - 1;
+    if (stream_word)
+        for (int32_t s = 0; s < e->n_streams; ++s)
+            if (stream_word[s] < 0 || stream_word[s] >= n_words)
+                return fail_word_index(stream_word[s], kOfStream, s, n_words);
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));    // the pushes so far keep their scoring
+    HIP_TRY(hipStreamSynchronize(e->sstream));
+    const size_t cap = (size_t)e->ev_cap;
+    const bool fresh = e->sb_list.p == nullptr;
+    HIP_TRY(e->sb_mean.reserve(cap * NMFCC));
+    HIP_TRY(e->sb_std.reserve(cap * NMFCC));
+    HIP_TRY(e->sb_theta.reserve(cap));
+    HIP_TRY(e->sb_mean64.reserve(cap * NMFCC));
+    HIP_TRY(e->sb_std64.reserve(cap * NMFCC));
+    HIP_TRY(e->sb_list.reserve(kEvListHdr + cap));
+    if (fresh) HIP_TRY(hipMemset(e->sb_list.p, 0, kEvListHdr * sizeof(int32_t)));
+    if (stream_word) {
+        HIP_TRY(e->sb_word.reserve((size_t)e->n_streams));
+        HIP_TRY(hipMemcpy(e->sb_word.p, stream_word, (size_t)e->n_streams * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    e->sbank_words = stream_word != nullptr;
+    e->sbank_on = true;
+    return EWK_OK;
+}
+
+int ewk_stream_bank_disable(ewk_engine* e) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (!e->sbank_on) return EWK_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipStreamSynchronize(e->sstream));
+    e->sbank_on = false;
+    return EWK_OK;
+}
+
+// ---- a push, stage by stage ---------------------------------------------------------
+// Host samples: gather the caller's (pageable) blocks into pinned staging on the CPU, then DMA
+// asynchronously on s -- the caller's buffer may die as soon as we return.
+static int stage_host_ticks(ewk_engine* e, TickSrc* src, int32_t rows, int32_t n_ticks, int64_t in_block,
+                            hipStream_t s) {
+    const size_t es = src->pcm16 ? sizeof(int16_t) : sizeof(float);
+    const unsigned char* pcm = static_cast<const unsigned char*>(src->p);
+    const size_t per_stream = (size_t)n_ticks * in_block;
+    const size_t total = per_stream * rows;
+    if (e->h_stage_free) HIP_TRY(hipEventSynchronize(e->h_stage_free));   // previous DMA done
+    if (total > e->h_stage_cap) {
+        if (e->h_stage) HIP_TRY(hipHostFree(e->h_stage));
+        e->h_stage = nullptr;
+        e->h_stage_cap = 0;
+        HIP_TRY(hipHostMalloc((void**)&e->h_stage, total * sizeof(float), hipHostMallocDefault));   // >= es bytes each
+        e->h_stage_cap = total;
+    }
+    if (!e->h_stage_free) HIP_TRY(hipEventCreateWithFlags(&e->h_stage_free, hipEventDisableTiming));
+    for (int32_t st = 0; st < rows; ++st)
+        for (int32_t t = 0; t < n_ticks; ++t)
+            memcpy(reinterpret_cast<unsigned char*>(e->h_stage) + ((size_t)st * per_stream + (size_t)t * in_block) * es,
+                   pcm + ((size_t)st * src->stride + (size_t)t * src->tick_stride) * es, in_block * es);
+    HIP_TRY(e->push_stage.reserve(total));
+    HIP_TRY(hipMemcpyAsync(e->push_stage.p, e->h_stage, total * es, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(e->h_stage_free, s));
+    *src = TickSrc{e->push_stage.p, src->pcm16, (int64_t)per_stream, in_block};
+    return EWK_OK;
+}
+
+// What every gate launch of one push shares: the engine's configuration and state arrays, and
+// the event bank pushes append to.  The launch loop adds the samples, the ticks and the clocks.
+static GateArgs gate_args(ewk_engine* e) {
+    GateArgs g;
+    memset(&g, 0, sizeof(g));
+    g.ring = e->ring_f32();
+    g.ring16 = e->ring_i16();
+    g.ring_len = e->ring_len;
+    g.sring_len = e->sring_len;
+    g.compact = e->sring_len < e->ring_len ? 1 : 0;
+    g.block_rms = e->d_brms;
+    g.sorted_rms = e->d_sorted;
+    g.trees = e->d_trees;
+    g.st = e->d_st;
+    g.block = e->cfg.block;
+    g.n_blocks = e->n_blocks;
+    g.n_last = e->n_last;
+    g.sample_rate = e->cfg.sample_rate;
+    g.stage = e->gate_stage;
+    g.val_len = e->gate_val_len;
+    g.tick_seconds = e->cfg.tick_seconds;
+    g.pre_speech_silence = e->cfg.pre_speech_silence;
+    g.speech_duration_min = e->cfg.speech_duration_min;
+    g.speech_duration_max = e->cfg.speech_duration_max;
+    g.post_speech_silence = e->cfg.post_speech_silence;
+    g.padding = e->cfg.padding;
+    g.max_segment_seconds = e->cfg.max_segment_seconds;
+    g.reentry_timeout = e->cfg.reentry_timeout;   // (ewk_reenter changes it between pushes)
+    g.min_threshold = e->cfg.min_threshold;
+    g.events = e->ev_bank(e->bank);
+    g.ev_count = e->evc_bank(e->bank);
+    g.ev_dropped = e->evc_bank(e->bank) + 1;
+    g.ev_cap = e->ev_cap;
+    return g;
+}
+
+// The scoring pass behind gate launch number push_seq (k = its parity) on s: beside the next gate
+// on sstream from a snapshot of the event count (overlap), or next in line on s.
+static int score_after_gate(ewk_engine* e, int k, hipStream_t s) {
+    if (!e->overlap) return score_pending(e, s, e->evc_bank(e->bank));
+    int32_t* snap = e->d_work + 4 + k;
+    HIP_TRY(launch_snapshot(e->evc_bank(e->bank), snap, s));
+    HIP_TRY(hipEventRecord(e->gate_evt[k], s));
+    HIP_TRY(hipStreamWaitEvent(e->sstream, e->gate_evt[k], 0));
+    int rc = score_pending(e, e->sstream, snap);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(e->score_evt[k], e->sstream));
+    e->score_live[k] = true;
+    e->score_tail = e->score_evt[k];
+    return EWK_OK;
+}
+
+// The poll mirror of this bank: written by the last scoring pass's tick end, or by k_bank_mirror:
+// behind the gate (no template yet: no scoring pass), or behind the stream bank's last pass (its
+// fp64 pass changes events after the tick end).  Then the bank's done event.
+static int finish_push(ewk_engine* e, hipStream_t s) {
+    hipStream_t ms = e->overlap ? e->sstream : s;
+    if (e->sbank_on || !e->has_tmpl) {
+        HIP_TRY(ensure_poll_region(e));
+        HIP_TRY(launch_bank_mirror(e->evc_bank(e->bank), e->ev_bank(e->bank), e->ev_base0[e->bank], e->ev_cap,
+                                   std::min<int32_t>(kPollChunk, e->ev_cap), e->d_poll + e->bank * kPollRegion, ms));
+    }
+    e->mirror[e->bank] = true;
+    HIP_TRY(hipEventRecord(e->bank_done[e->bank], ms));
+    e->bank_used[e->bank] = true;
+    return EWK_OK;
+}
+
+// streams == nullptr: a tick for every stream (row s of pcm is stream s); else rows 0..n_list-1
+// are the ticks of streams[0..n_list) (ewk_push_streams).
+static int push_impl(ewk_engine* e, const void* pcm_any, int64_t stride, int64_t tick_stride, int32_t n_ticks,
+                     int32_t flags, bool pcm16, const int32_t* streams = nullptr, int32_t n_list = 0) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (e->n_streams <= 0) return fail(EWK_EINVAL, "engine has no streams");
+    if (streams || n_list) {   // (validated before anything is enqueued or changed)
+        int rc = check_stream_list(e, streams, n_list);
+        if (rc) return rc;
+    }
+    const int32_t rows = streams ? n_list : e->n_streams;
+    if (!pcm_any) return fail(EWK_EINVAL, "pcm is NULL");
+    if (n_ticks <= 0) return fail(EWK_EINVAL, "n_ticks must be positive");
+    if (!pcm16 && e->ring_es == sizeof(int16_t))
+        return fail(EWK_EINVAL, "an int16 ring (EWK_RING_I16) takes PCM16 pushes (ewk_push_pcm16)");
+    // with an input rate set (ewk_set_input_rate) a tick is in_block samples at that rate
+    const int64_t in_block = e->rs_on ? e->rs_in_block : e->cfg.block;
+    if (stride < in_block && rows > 1)
+        return fail(EWK_EINVAL, e->rs_on ? "stride must be >= the input block (ewk_input_rate_info)" : "stride must be >= block");
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    int rc = EWK_OK;
+    const int32_t* d_list = nullptr;
+    if (streams) {
+        rc = desynchronise(e, s);
+        if (rc == EWK_OK) rc = stage_stream_list(e, streams, nullptr, n_list, s, &d_list, nullptr);
+    }
+    TickSrc src{pcm_any, pcm16, stride, tick_stride};
+    if (rc == EWK_OK && !(flags & EWK_PUSH_DEVICE)) rc = stage_host_ticks(e, &src, rows, n_ticks, in_block, s);
+    if (rc == EWK_OK && e->rs_on) rc = resample_ticks(e, &src, rows, n_ticks, d_list, s);
+    if (rc) return rc;
+    GateArgs g = gate_args(e);
+    g.stride = src.stride;
+    g.tick_stride = src.tick_stride;
+    g.n_streams = rows;
+    g.ids = d_list;
+    // Segments must be scored before the ring overwrites them: <= ticks_per_launch ticks per gate launch.
+    for (int32_t t0 = 0; t0 < n_ticks; t0 += e->ticks_per_launch) {
+        const int32_t nt = std::min<int32_t>(e->ticks_per_launch, n_ticks - t0);
+        if (src.pcm16) g.pcm16 = static_cast<const int16_t*>(src.p) + (int64_t)t0 * src.tick_stride;
+        else g.pcm = static_cast<const float*>(src.p) + (int64_t)t0 * src.tick_stride;
+        g.n_ticks = nt;
+        g.own_clock = e->desync ? 1 : 0;
+        g.tick0 = e->tick;
+        g.ev_base0 = e->ev_base0[e->bank];
+        const int k = (int)(e->push_seq & 1);
+        // the scoring pass two launches back must be done: it read snapshot slot k, and
+        // at most one pass runs beside a gate
+        if (e->overlap && e->score_live[k]) HIP_TRY(hipStreamWaitEvent(s, e->score_evt[k], 0));
+        {
+            ProfScope ps(e, 2, s);
+            HIP_TRY(launch_gate(g, s));
+        }
+        if (!streams) e->tick += nt;
+        else for (int32_t i = 0; i < n_list; ++i) e->tick_delta[streams[i]] += nt;
+        rc = score_after_gate(e, k, s);
+        if (rc) return rc;
+        e->push_seq += 1;
+    }
+    return finish_push(e, s);
+}
+
+int ewk_push(ewk_engine* e, const float* pcm, int64_t stride, int32_t flags) {
+    return push_impl(e, pcm, stride, 0, 1, flags, false);
+}
+
+int ewk_push_many(ewk_engine* e, const float* pcm, int64_t stride, int64_t tick_stride, int32_t n_ticks,
+                  int32_t flags) {
+    return push_impl(e, pcm, stride, tick_stride, n_ticks, flags, false);
+}
+
+int ewk_push_pcm16(ewk_engine* e, const int16_t* pcm, int64_t stride, int32_t flags) {
+    return push_impl(e, pcm, stride, 0, 1, flags, true);
+}
+
+int ewk_push_many_pcm16(ewk_engine* e, const int16_t* pcm, int64_t stride, int64_t tick_stride, int32_t n_ticks,
+                        int32_t flags) {
+    return push_impl(e, pcm, stride, tick_stride, n_ticks, flags, true);
+}
+
+// ---------------------------------------------------------------- stream lifecycle
+int ewk_push_streams(ewk_engine* e, const int32_t* streams, int32_t n, const float* pcm, int64_t stride,
+                     int64_t tick_stride, int32_t n_ticks, int32_t flags) {
+    if (e && !streams) return fail(EWK_EINVAL, "streams is NULL");
+    return push_impl(e, pcm, stride, tick_stride, n_ticks, flags, false, streams, n);
+}
+
+int ewk_push_streams_pcm16(ewk_engine* e, const int32_t* streams, int32_t n, const int16_t* pcm, int64_t stride,
+                           int64_t tick_stride, int32_t n_ticks, int32_t flags) {
+    if (e && !streams) return fail(EWK_EINVAL, "streams is NULL");
+    return push_impl(e, pcm, stride, tick_stride, n_ticks, flags, true, streams, n);
+}
+
+int ewk_reset_stream_list(ewk_engine* e, const int32_t* streams, int32_t n) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (e->n_streams <= 0) return fail(EWK_EINVAL, "engine has no streams");
+    int rc = check_stream_list(e, streams, n);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    HIP_TRY(join_scoring(e, s));   // (overlap mode: the scorer may still read these ring rows)
+    rc = desynchronise(e, s);
+    if (rc) return rc;
+    ResetListArgs a;
+    memset(&a, 0, sizeof(a));
+    rc = stage_stream_list(e, streams, nullptr, n, s, &a.ids, nullptr);
+    if (rc) return rc;
+    a.n = n;
+    a.ring = static_cast<unsigned char*>(e->d_ring);
+    a.row_bytes = e->sring_len * (int64_t)e->ring_es;
+    a.block_rms = e->d_brms;
+    a.n_blocks = e->n_blocks;
+    a.st = e->d_st;
+    a.init_threshold = e->cfg.initial_threshold;
+    if (e->rs_on) {   // (a rate set earlier and switched off again: set_input_rate clears every row)
+        a.hist = e->rs_hist.p;
+        a.H = e->rs_in.H;
+        a.fresh = e->rs_flags.p;
+    }
+    HIP_TRY(launch_reset_list(a, s));
+    for (int32_t i = 0; i < n; ++i) e->tick_delta[streams[i]] = -e->tick;
+    return EWK_OK;
+}
+
+int ewk_stream_ticks(ewk_engine* e, const int32_t* streams, int32_t n, int64_t* out) {
+    if (!e || !out) return fail(EWK_EINVAL, "NULL argument");
+    if (n < 0 || n > e->n_streams)
+        return fail(EWK_EINVAL, "n must be in [0, " + std::to_string(e->n_streams) + "]");
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t s = streams ? streams[i] : i;
+        if (s < 0 || s >= e->n_streams) return fail_stream_index(e, i, s);
+    }
+    for (int32_t i = 0; i < n; ++i) out[i] = e->stream_tick(streams ? streams[i] : i);
+    return EWK_OK;
+}
+
+int ewk_stream_bank_assign(ewk_engine* e, const int32_t* streams, int32_t n, const int32_t* words) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (!e->sbank_on) return fail(EWK_EINVAL, "the stream bank is off (ewk_stream_bank_enable)");
+    int rc = check_stream_list(e, streams, n);
+    if (rc) return rc;
+    if (!words) return fail(EWK_EINVAL, "words is NULL");
+    const int32_t n_words = (int32_t)e->bank_first.size() - 1;
+    for (int32_t i = 0; i < n; ++i)
+        if (words[i] < 0 || words[i] >= n_words) return fail_word_index(words[i], kOfStream, streams[i], n_words);
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    HIP_TRY(join_scoring(e, s));   // (overlap mode: a scoring pass in flight still reads the words)
+    if (!e->sbank_words) {   // enabled with word 0 for every stream: the array, all zeros
+        HIP_TRY(e->sb_word.reserve((size_t)e->n_streams));
+        HIP_TRY(hipMemsetAsync(e->sb_word.p, 0, (size_t)e->n_streams * sizeof(int32_t), s));
+        e->sbank_words = true;
+    }
+    const int32_t *d_list = nullptr, *d_vals = nullptr;
+    rc = stage_stream_list(e, streams, words, n, s, &d_list, &d_vals);
+    if (rc) return rc;
+    HIP_TRY(launch_scatter_i32(e->sb_word.p, d_list, d_vals, n, s));
+    return EWK_OK;
+}
+
+// Event banks are drained in two steps so a failing poll consumes nothing:
+// peek_bank waits for the pushes into bank b (copy stream only, no wait on later
+// work) and fetches its counters with the first kPollChunk events; take_bank copies
+// the rest out and re-arms the bank's counters on the engine stream.
+struct BankPeek {
+    int32_t n = 0;         // queued events (<= ev_cap)
+    int32_t dropped = 0;   // events lost to a full bank
+    uint32_t count = 0, dropped_total = 0;   // the raw counters (the next epoch's bases)
+    bool used = false;
+};
+
+static int peek_bank(ewk_engine* e, int b, BankPeek* pk) {
+    *pk = BankPeek();
+    if (!e->bank_used[b]) return EWK_OK;
+    HIP_TRY(ensure_poll_region(e));
+    unsigned char* reg = e->h_poll + b * kPollRegion;
+    int32_t* cnt = reinterpret_cast<int32_t*>(reg);
+    const int32_t chunk = std::min<int32_t>(kPollChunk, e->ev_cap);
+    if (e->mirror[b]) {   // written by k_bank_mirror behind the bank's last push
+        HIP_TRY(hipEventSynchronize(e->bank_done[b]));
+    } else {
+        HIP_TRY(hipStreamWaitEvent(e->cstream, e->bank_done[b], 0));
+        HIP_TRY(hipMemcpyAsync(cnt, e->evc_bank(b), 4 * sizeof(int32_t), hipMemcpyDeviceToHost, e->cstream));
+        HIP_TRY(hipMemcpyAsync(reg + 16, e->ev_bank(b), (size_t)chunk * sizeof(ewk_event), hipMemcpyDeviceToHost,
+                               e->cstream));
+        HIP_TRY(hipStreamSynchronize(e->cstream));
+    }
+    pk->count = (uint32_t)cnt[0];
+    pk->dropped_total = (uint32_t)cnt[1];
+    pk->n = (int32_t)std::min<uint32_t>(pk->count - e->ev_base0[b], (uint32_t)e->ev_cap);
+    pk->dropped = (int32_t)(pk->dropped_total - e->drop_base0[b]);
+    pk->used = true;
+    return EWK_OK;
+}
+
+// Re-arm bank b: its next epoch starts at the counters the host just read (no device work;
+// the scorer's watermark is at or behind the new base and is clamped to it).
+static int rearm_bank(ewk_engine* e, int b, const BankPeek& pk) {
+    e->ev_base0[b] = pk.count;
+    e->drop_base0[b] = pk.dropped_total;
+    e->bank_used[b] = false;
+    e->mirror[b] = false;
+    return EWK_OK;
+}
+
+static int take_bank(ewk_engine* e, int b, const BankPeek& pk, ewk_event* out) {
+    if (!pk.used) return EWK_OK;
+    const int32_t chunk = std::min<int32_t>(kPollChunk, e->ev_cap);
+    if (pk.n > 0 && out) {
+        memcpy(out, e->h_poll + b * kPollRegion + 16, (size_t)std::min(pk.n, chunk) * sizeof(ewk_event));
+        if (pk.n > chunk) {
+            HIP_TRY(hipMemcpyAsync(out + chunk, e->ev_bank(b) + chunk, (size_t)(pk.n - chunk) * sizeof(ewk_event),
+                                   hipMemcpyDeviceToHost, e->cstream));
+            HIP_TRY(hipStreamSynchronize(e->cstream));
+        }
+    }
+    return rearm_bank(e, b, pk);
+}
+
+// An overflowed bank cannot be delivered whole: re-arm it (its events are lost, the
+// engine keeps running) and report how many were dropped.
+static int overflow(ewk_engine* e, const BankPeek* pk, const int* banks, int nb) {
+    int64_t lost = 0;
+    for (int i = 0; i < nb; ++i)
+        if (pk[i].used && pk[i].dropped > 0) {
+            lost += (int64_t)pk[i].n + pk[i].dropped;
+            int rc = rearm_bank(e, banks[i], pk[i]);
+            if (rc) return rc;
+        }
+    return fail(EWK_ENOMEM, "event queue overflow: " + std::to_string(lost) +
+                                " events of the overflowed bank(s) dropped; the queue was re-armed");
+}
+
+static void sort_events(ewk_event* out, int32_t n) {   // deterministic order: (tick, stream)
+    std::sort(out, out + n, [](const ewk_event& x, const ewk_event& y) {
+        return x.tick != y.tick ? x.tick < y.tick : x.stream < y.stream;
+    });
+}
+
+static int poll_banks(ewk_engine* e, const int* banks, int nb, ewk_event* out, int32_t cap, int32_t* n_out) {
+    BankPeek pk[2];
+    int64_t total = 0;
+    bool over = false;
+    for (int i = 0; i < nb; ++i) {
+        int rc = peek_bank(e, banks[i], &pk[i]);
+        if (rc) return rc;
+        total += pk[i].n;
+        over = over || pk[i].dropped > 0;
+    }
+    if (over) return overflow(e, pk, banks, nb);
+    // validated before either bank is consumed: a short `cap` loses nothing
+    if (out && total > std::max(0, cap))
+        return fail(EWK_EINVAL, "poll capacity " + std::to_string(cap) + " is smaller than the " +
+                                    std::to_string(total) + " queued events (nothing was drained)");
+    int32_t n = 0;
+    for (int i = 0; i < nb; ++i) {
+        int rc = take_bank(e, banks[i], pk[i], out ? out + n : nullptr);
+        if (rc) return rc;
+        n += pk[i].n;
+    }
+    if (out) sort_events(out, n);
+    *n_out = n;
+    return EWK_OK;
+}
+
+int ewk_poll(ewk_engine* e, ewk_event* out, int32_t cap, int32_t* n_out) {
+    if (!e || !n_out) return fail(EWK_EINVAL, "NULL argument");
+    *n_out = 0;
+    if (e->n_streams <= 0) return EWK_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    const int banks[2] = {e->bank ^ 1, e->bank};   // older first
+    return poll_banks(e, banks, 2, out, cap, n_out);
+}
+
+int ewk_poll_lagged(ewk_engine* e, ewk_event* out, int32_t cap, int32_t* n_out) {
+    if (!e || !n_out) return fail(EWK_EINVAL, "NULL argument");
+    *n_out = 0;
+    if (e->n_streams <= 0) return EWK_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    const int older = e->bank ^ 1;
+    const int banks[1] = {older};
+    int rc = poll_banks(e, banks, 1, out, cap, n_out);
+    if (rc == EWK_OK || !e->bank_used[older])   // drained (or re-armed after an overflow)
+        e->bank = older;   // later pushes append to the drained bank; the newest one drains next time
+    return rc;
+}
+
+int ewk_reenter(ewk_engine* e, int32_t stream, double reentry_timeout) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (e->n_streams <= 0) return fail(EWK_EINVAL, "engine has no streams");
+    if (stream < -1 || stream >= e->n_streams) return fail(EWK_EINVAL, "stream index out of range");
+    if (!(reentry_timeout == reentry_timeout)) return fail(EWK_EINVAL, "reentry_timeout is NaN");
+    HIP_TRY(hipSetDevice(e->device));
+    e->cfg.reentry_timeout = reentry_timeout;   // read by every later gate launch
+    const int32_t first = stream < 0 ? 0 : stream;
+    const int32_t n = stream < 0 ? e->n_streams : 1;
+    HIP_TRY(launch_reenter(e->d_st, first, n, e->cfg.tick_seconds, e->stream));
+    return EWK_OK;
+}
+
+int ewk_get_stream_state(ewk_engine* e, int32_t stream, ewk_stream_state* out) {
+    if (!e || !out) return fail(EWK_EINVAL, "NULL argument");
+    if (stream < 0 || stream >= e->n_streams) return fail(EWK_EINVAL, "stream index out of range");
+    HIP_TRY(hipSetDevice(e->device));
+    GateStream st;
+    HIP_TRY(hipMemcpyAsync(&st, e->d_st + stream, sizeof(st), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    out->samples_collected = st.collected;
+    out->tick = st.tick;
+    out->silence_threshold = st.threshold;
+    out->last_rms = st.last_rms;
+    out->silence_start_time = st.silence_start;
+    out->sound_start_time = st.sound_start;
+    out->sound_end_time = st.sound_end;
+    out->start_time = st.start_time;
+    out->pointer = st.pointer;
+    out->state = st.state;
+    out->started = st.started;
+    out->last_silent = st.last_silent;
+    return EWK_OK;
+}
+
+int ewk_read_segment(ewk_engine* e, int32_t stream, int64_t ring_start, int32_t length, float* out) {
+    if (!e || !out) return fail(EWK_EINVAL, "NULL argument");
+    if (stream < 0 || stream >= e->n_streams) return fail(EWK_EINVAL, "stream index out of range");
+    if (length < 0 || length > e->sring_len || ring_start < 0 || ring_start >= e->sring_len)
+        return fail(EWK_EINVAL, "segment out of range");
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t es = e->ring_es;
+    const unsigned char* base = static_cast<const unsigned char*>(e->d_ring) + (size_t)stream * e->sring_len * es;
+    const int64_t first = std::min<int64_t>(length, e->sring_len - ring_start);
+    // int16 rings: copied to a host staging buffer, then widened (x / 32768, exact)
+    std::vector<int16_t> q(es == sizeof(int16_t) ? (size_t)length : 0);
+    unsigned char* dst = es == sizeof(float) ? reinterpret_cast<unsigned char*>(out)
+                                             : reinterpret_cast<unsigned char*>(q.data());
+    HIP_TRY(hipMemcpyAsync(dst, base + ring_start * es, first * es, hipMemcpyDeviceToHost, e->stream));
+    if (length > first)
+        HIP_TRY(hipMemcpyAsync(dst + first * es, base, (length - first) * es, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (size_t i = 0; i < q.size(); ++i) out[i] = (float)q[i] * (1.0f / 32768.0f);
+    return EWK_OK;
+}
+
+int ewk_read_last(ewk_engine* e, int32_t stream, int64_t n_samples, float* out, int64_t* n_out) {
+    if (!e || !out || !n_out) return fail(EWK_EINVAL, "NULL argument");
+    if (stream < 0 || stream >= e->n_streams) return fail(EWK_EINVAL, "stream index out of range");
+    // return_last_n_seconds: at most the reference ring (wakeword.py:500-502)
+    int64_t n = std::min<int64_t>(std::max<int64_t>(n_samples, 0), e->ring_len);
+    *n_out = 0;
+    if (n > e->sring_len)
+        return fail(EWK_EINVAL, "the compact ring keeps only the last " + std::to_string(e->sring_len) + " samples");
+    HIP_TRY(hipSetDevice(e->device));
+    GateStream st;
+    HIP_TRY(hipMemcpyAsync(&st, e->d_st + stream, sizeof(st), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    *n_out = n;
+    if (n == 0) return EWK_OK;
+    int64_t start = st.spos - n;
+    if (start < 0) start += e->sring_len;
+    return ewk_read_segment(e, stream, start, (int32_t)n, out);
+}

@@ -423,8 +423,12 @@ int ewk_set_input_rate(ewk_engine* e, int32_t in_rate);
 int ewk_input_rate_info(ewk_engine* e, int32_t* in_rate, int32_t* in_block, int32_t* delay);
 
 /* ---- measurement ------------------------------------------------------------ */
-/* When enabled, every scorer / gate launch is bracketed by hipEvents on the
- * stream it runs on; ewk_profile_read resolves them (synchronizing) and returns
+/* When enabled, these launches are bracketed by hipEvents on the stream they run on:
+ * the scorer and re-score launches of ewk_score_segments_device, of the bank scoring
+ * calls (host and device pointers) and of every streaming scoring pass, every gate
+ * launch, and the resampler.  The host-copy calls ewk_score_segments and
+ * ewk_score_segments_f64 (so ewk_template_from_pcm and ewk_bank_from_pcm too) launch
+ * without brackets.  ewk_profile_read resolves them (synchronizing) and returns
  * the summed device time and launch count per kernel family, then clears.
  * kind: 0 = fp32 MFCC scorer (k_score_f32), 1 = fp64 re-scorer, 2 = gate ticks,
  * 3 = resampler launches (ewk_resample, and the resample + history save of a push). */

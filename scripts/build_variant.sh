@@ -1,30 +1,25 @@
 #!/bin/bash
 # Build libewk.so from a git revision (or the working tree with "WT") into variants/<name>.so,
 # optionally with extra -D flags:  scripts/build_variant.sh <rev|WT> <name> [-DFOO=1 ...]
+# The sources are every *.hip and *.cpp the revision has in csrc/ (beside every header there).
 set -e
 R="$(cd "$(dirname "$0")/.." && pwd)"
 REV=$1; NAME=$2; shift 2
+C=easywakeword_amd/csrc
 T=$(mktemp -d)
-mkdir -p "$T/easywakeword_amd/csrc" "$T/include" "$R/variants"
-SRCS="ewk_mfcc.hip ewk_gate.hip ewk_level3.hip ewk_engine.cpp ewk_tables.cpp"
-for f in easywakeword_amd/csrc/ewk_gather.hip; do   # sources that older revisions lack
-  if [ "$REV" = "WT" ] || git -C "$R" cat-file -e "$REV:$f" 2>/dev/null; then SRCS="$SRCS $(basename $f)"; fi
-done
-HDRS="ewk_internal.h ewk_gate.h"
-for h in ewk_rescore.h ewk_fp4.h ewk_fp4_mel.h ewk_db64.h ewk_topdb_shift.h; do   # headers that some revisions lack (ewk_fp4*.h: round 5 only)
-  if { [ "$REV" = "WT" ] && [ -f "$R/easywakeword_amd/csrc/$h" ]; } || \
-     { [ "$REV" != "WT" ] && git -C "$R" cat-file -e "$REV:easywakeword_amd/csrc/$h" 2>/dev/null; }; then HDRS="$HDRS $h"; fi
-done
-for s in $SRCS $HDRS; do
-  f=easywakeword_amd/csrc/$s
-  if [ "$REV" = "WT" ]; then cp "$R/$f" "$T/$f"; else git -C "$R" show "$REV:$f" > "$T/$f"; fi
-done
-if [ "$REV" = "WT" ]; then cp "$R/include/ewk.h" "$T/include/ewk.h"; else git -C "$R" show "$REV:include/ewk.h" > "$T/include/ewk.h"; fi
+mkdir -p "$T/$C" "$T/include" "$R/variants"
+if [ "$REV" = "WT" ]; then
+  cp "$R/$C"/*.hip "$R/$C"/*.cpp "$R/$C"/*.h "$T/$C/"
+  cp "$R/include/ewk.h" "$T/include/ewk.h"
+else
+  git -C "$R" archive "$REV" "$C" include/ewk.h | tar -x -C "$T"
+fi
 objs=""
-for s in $SRCS; do
+for f in "$T/$C"/*.hip "$T/$C"/*.cpp; do
+  s=$(basename "$f")
   x=""; [ "$s" = ewk_mfcc.hip ] && x="-fno-slp-vectorize"   # as easywakeword_amd/build.py EXTRA
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-function $x "$@" \
-     -c "$T/easywakeword_amd/csrc/$s" -o "$T/$s.o" &
+     -c "$f" -o "$T/$s.o" &
   objs="$objs $T/$s.o"
 done
 wait
