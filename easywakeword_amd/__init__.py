@@ -7,11 +7,11 @@ MFCC + cosine matcher, as hand-written HIP kernels behind a C ABI
 
     from easywakeword_amd import WakeWord, WordMatcher, StreamEngine
 """
-from .engine import Engine, StreamEngine
-from .wakeword import SoundBuffer, WakeWord, WordMatcher
+from .engine import DetectorProfile, Engine, StreamEngine
+from .wakeword import SoundBuffer, WakeWord, WordMatcher, detector_profile
 from .audio import ArraySource, WavSource, load_wav, write_wav
 from .devices import AudioDeviceManager
 
-__all__ = ["WakeWord", "WordMatcher", "SoundBuffer", "Engine", "StreamEngine",
+__all__ = ["WakeWord", "WordMatcher", "SoundBuffer", "Engine", "StreamEngine", "DetectorProfile", "detector_profile",
            "ArraySource", "WavSource", "load_wav", "write_wav", "AudioDeviceManager"]
 __version__ = "0.1.0"

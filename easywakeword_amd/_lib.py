@@ -44,6 +44,7 @@ EWK_SCORE_F32_CANDIDATES = 2
 EWK_COMPACT_APPEND = 1
 EWK_BANK_MAX_PER_WORD = 64
 EWK_BANK_MAX_TEMPLATES = 65536
+EWK_PROFILE_MAX = 65536
 
 # Every symbol include/ewk.h declares (checked by tests/test_capi.py).
 EXPORTS = [
@@ -62,6 +63,8 @@ EXPORTS = [
     "ewk_resample_design", "ewk_resample", "ewk_set_input_rate", "ewk_input_rate_info",
     "ewk_push_streams", "ewk_push_streams_pcm16", "ewk_reset_stream_list", "ewk_stream_ticks",
     "ewk_stream_bank_assign",
+    "ewk_default_detector_profile", "ewk_detector_profiles_set", "ewk_detector_profiles_info",
+    "ewk_detector_profile_get", "ewk_stream_profile_assign", "ewk_stream_profiles",
 ]
 
 
@@ -75,6 +78,18 @@ class EwkConfig(C.Structure):
         ("initial_threshold", C.c_double), ("rescore_margin", C.c_double),
         ("ring_format", C.c_int32), ("reserved1", C.c_int32),
     ]
+
+
+class EwkDetectorProfile(C.Structure):
+    """ewk_detector_profile: the per-WakeWord gate timings of EwkConfig (56 bytes)."""
+    _fields_ = [
+        ("pre_speech_silence", C.c_double), ("speech_duration_min", C.c_double), ("speech_duration_max", C.c_double),
+        ("post_speech_silence", C.c_double), ("padding", C.c_double), ("max_segment_seconds", C.c_double),
+        ("reentry_timeout", C.c_double),
+    ]
+
+
+PROFILE_FIELDS = tuple(f for f, _ in EwkDetectorProfile._fields_)
 
 
 class EwkEvent(C.Structure):
@@ -205,6 +220,12 @@ def load():
             "ewk_reset_stream_list": (C.c_int, [_P, _i32p, C.c_int32]),
             "ewk_stream_ticks": (C.c_int, [_P, _i32p, C.c_int32, _i64p]),
             "ewk_stream_bank_assign": (C.c_int, [_P, _i32p, C.c_int32, _i32p]),
+            "ewk_default_detector_profile": (None, [_P, C.POINTER(EwkDetectorProfile)]),
+            "ewk_detector_profiles_set": (C.c_int, [_P, C.POINTER(EwkDetectorProfile), C.c_int32]),
+            "ewk_detector_profiles_info": (C.c_int, [_P, _i32p]),
+            "ewk_detector_profile_get": (C.c_int, [_P, C.c_int32, C.POINTER(EwkDetectorProfile)]),
+            "ewk_stream_profile_assign": (C.c_int, [_P, _i32p, C.c_int32, _i32p]),
+            "ewk_stream_profiles": (C.c_int, [_P, _i32p, C.c_int32, _i32p]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)

@@ -25,6 +25,28 @@ hipEvent_t ewk::pool_event(ewk_engine* e) {
     return x;
 }
 
+// Longest segment request the cut can make (wakeword.py:1100-1111): nreq =
+// int(|sound_start - now - padding| * sr) with now - sound_start <= max speech +
+// (post silence rounded up to a tick), capped at the ring (return_last_n_seconds).
+int64_t ewk::segment_need(const ewk_config& c, int64_t ring_len, double speech_duration_max,
+                          double post_speech_silence, double padding) {
+    return std::min<int64_t>(ring_len, (int64_t)((speech_duration_max + post_speech_silence + c.tick_seconds + padding) *
+                                                 (double)c.sample_rate) + 2);
+}
+
+// A segment is cut at the tick that ends it and scored after its gate launch,
+// so the ticks of one launch after the cut must not reach its first sample:
+// ticks_per_launch <= (ring - longest request) / block (>= 1: a one-tick launch is
+// always safe, the cut never asks for more than the ring).  Overlapping the
+// scoring with the next gate launch doubles the ticks that may pass.
+void ewk::set_launch_ticks(ewk_engine* e, int64_t seg_need) {
+    const int64_t room = (e->sring_len - std::min(seg_need, e->sring_len)) / (int64_t)e->cfg.block;
+    const int64_t tpl = std::max<int64_t>(1, std::min<int64_t>(32, room));
+    const int64_t tpl_ov = std::min<int64_t>(32, room / 2);
+    e->overlap = tpl_ov >= 1 && e->overlap_want;
+    e->ticks_per_launch = (int32_t)(e->overlap ? tpl_ov : tpl);
+}
+
 // Order stream s after every ring-mode scoring pass enqueued so far (they run on
 // sstream): needed before touching what those passes read or share -- the template,
 // the re-score list, the log-mel and fp64 scratch, the event banks.
@@ -173,12 +195,7 @@ int ewk_create(ewk_engine** out, int device, int32_t n_streams, const ewk_config
         return fail(EWK_EINVAL, "ring_format must be EWK_RING_F32 or EWK_RING_I16");
     const int64_t ring_len = (int64_t)c.buffer_seconds * c.sample_rate;
     if (ring_len > INT32_MAX / 2) return fail(EWK_EINVAL, "buffer_seconds too large");
-    // Longest segment request the cut can make (wakeword.py:1100-1111): nreq =
-    // int(|sound_start - now - padding| * sr) with now - sound_start <= max speech +
-    // (post silence rounded up to a tick), capped at the ring (return_last_n_seconds).
-    const int64_t seg_need = std::min<int64_t>(
-        ring_len, (int64_t)((c.speech_duration_max + c.post_speech_silence + c.tick_seconds + c.padding) *
-                            (double)c.sample_rate) + 2);
+    const int64_t seg_need = segment_need(c, ring_len, c.speech_duration_max, c.post_speech_silence, c.padding);
     if (c.ring_samples != 0) {
         if (c.ring_samples < 0 || c.ring_samples > ring_len)
             return fail(EWK_EINVAL, "ring_samples must be in [0, buffer_seconds * sample_rate]");
@@ -281,19 +298,20 @@ int ewk_create(ewk_engine** out, int device, int32_t n_streams, const ewk_config
             return bail(err, "events");
         if ((err = hipMalloc(&e->d_evc, 8 * sizeof(int32_t))) != hipSuccess) return bail(err, "event counters");
         e->gate_stage = gate_stage_len(c.block, e->n_last);
-        {   // A segment is cut at the tick that ends it and scored after its gate launch,
-            // so the ticks of one launch after the cut must not reach its first sample:
-            // ticks_per_launch <= (ring - longest request) / block (>= 1: a one-tick launch is
-            // always safe, the cut never asks for more than the ring).  Overlapping the
-            // scoring with the next gate launch doubles the ticks that may pass.
-            const int64_t room = (e->sring_len - std::min(seg_need, e->sring_len)) / (int64_t)c.block;
-            const int64_t tpl = std::max<int64_t>(1, std::min<int64_t>(32, room));
-            const int64_t tpl_ov = std::min<int64_t>(32, room / 2);
+        {
             // opt-in (EWK_SCORE_OVERLAP=1): measured on MI355X the extra stream/event calls
             // per tick cost more host time than the concurrency saves (scripts/mb_stream.py)
             const char* env = getenv("EWK_SCORE_OVERLAP");
-            e->overlap = tpl_ov >= 1 && env && env[0] == '1';
-            e->ticks_per_launch = (int32_t)(e->overlap ? tpl_ov : tpl);
+            e->overlap_want = env && env[0] == '1';
+            set_launch_ticks(e, seg_need);
+            // EWK_GATE_GRID_MAX=<workgroups>: a smaller gate grid than the built-in maximum (a wave
+            // then walks several streams at sizes a test can afford); unset or invalid: the maximum
+            const char* cap = getenv("EWK_GATE_GRID_MAX");
+            if (cap && cap[0]) {
+                char* end = nullptr;
+                const long v = strtol(cap, &end, 10);
+                if (end && *end == 0 && v > 0 && v <= INT32_MAX) e->gate_grid_cap = (int32_t)v;
+            }
         }
         int rc = ewk_reset_streams(e);
         if (rc != EWK_OK) {

@@ -155,6 +155,7 @@ struct ewk_engine {
     hipEvent_t score_tail = nullptr;                // the latest recorded score_evt
     int64_t push_seq = 0;
     bool overlap = false;
+    bool overlap_want = false;                      // EWK_SCORE_OVERLAP=1 at ewk_create (overlap: and the ring has the room)
     int32_t ticks_per_launch = 32;                  // gate launch length (segments must outlive it in the ring)
     ewk_event* ev_bank(int b) { return d_events + (size_t)b * ev_cap; }
     int32_t* evc_bank(int b) { return d_evc + 4 * b; }
@@ -181,6 +182,15 @@ struct ewk_engine {
     ewk::DevBuf<int32_t> d_ids;        // [2 * n_streams]
     hipEvent_t h_ids_free = nullptr;   // recorded after the last DMA out of h_ids
     int64_t stream_tick(int32_t s) const { return tick + (desync ? tick_delta[s] : 0); }
+    // Detector profiles (ewk_detector_profiles_set): the table as set and on the device, and the
+    // profile of every stream (-1: cfg) on the device with its host mirror; both per-stream arrays
+    // are allocated when a table is first set and empty / all -1 without one.  ticks_per_launch
+    // then follows the largest segment request over cfg and the table (set_launch_ticks).
+    std::vector<ewk_detector_profile> profiles;
+    ewk::DevBuf<ewk_detector_profile> d_profiles;
+    ewk::DevBuf<int32_t> d_stream_profile;    // [n_streams]
+    std::vector<int32_t> stream_profile;      // [n_streams]
+    int32_t gate_grid_cap = 0;      // EWK_GATE_GRID_MAX at ewk_create: workgroups per gate launch (0: the built-in maximum)
     int32_t gate_stage = 0;
     int32_t gate_val_len = 0;       // per-wave LDS doubles of the gate (tree values, sort scratch)
 
@@ -241,6 +251,10 @@ struct TickSrc {
 // ewk_engine.cpp
 hipError_t join_scoring(ewk_engine* e, hipStream_t s);
 hipError_t reserve_rescore(ewk_engine* e, int32_t n_seg);
+// the longest segment request of a set of timings, and the gate launch length (with `overlap`) it allows
+int64_t segment_need(const ewk_config& c, int64_t ring_len, double speech_duration_max, double post_speech_silence,
+                     double padding);
+void set_launch_ticks(ewk_engine* e, int64_t seg_need);
 // ewk_engine_score.cpp
 ScoreArgs base_args(ewk_engine* e);
 BankArgs bank_args(ewk_engine* e);

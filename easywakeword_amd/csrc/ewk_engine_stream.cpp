@@ -322,6 +322,10 @@ static GateArgs gate_args(ewk_engine* e) {
     g.ev_count = e->evc_bank(e->bank);
     g.ev_dropped = e->evc_bank(e->bank) + 1;
     g.ev_cap = e->ev_cap;
+    if (!e->profiles.empty()) {   // (else nullptr: the gate without the profile code)
+        g.profiles = e->d_profiles.p;
+        g.stream_profile = e->d_stream_profile.p;
+    }
     return g;
 }
 
@@ -408,7 +412,7 @@ static int push_impl(ewk_engine* e, const void* pcm_any, int64_t stride, int64_t
         if (e->overlap && e->score_live[k]) HIP_TRY(hipStreamWaitEvent(s, e->score_evt[k], 0));
         {
             ProfScope ps(e, 2, s);
-            HIP_TRY(launch_gate(g, s));
+            HIP_TRY(launch_gate(g, s, e->gate_grid_cap));
         }
         if (!streams) e->tick += nt;
         else for (int32_t i = 0; i < n_list; ++i) e->tick_delta[streams[i]] += nt;
@@ -514,6 +518,147 @@ int ewk_stream_bank_assign(ewk_engine* e, const int32_t* streams, int32_t n, con
     rc = stage_stream_list(e, streams, words, n, s, &d_list, &d_vals);
     if (rc) return rc;
     HIP_TRY(launch_scatter_i32(e->sb_word.p, d_list, d_vals, n, s));
+    return EWK_OK;
+}
+
+// ---------------------------------------------------------------- detector profiles
+static ewk_detector_profile profile_of_config(const ewk_config& c) {
+    ewk_detector_profile p;
+    p.pre_speech_silence = c.pre_speech_silence;
+    p.speech_duration_min = c.speech_duration_min;
+    p.speech_duration_max = c.speech_duration_max;
+    p.post_speech_silence = c.post_speech_silence;
+    p.padding = c.padding;
+    p.max_segment_seconds = c.max_segment_seconds;
+    p.reentry_timeout = c.reentry_timeout;
+    return p;
+}
+
+void ewk_default_detector_profile(const ewk_engine* e, ewk_detector_profile* out) {
+    if (!out) return;
+    if (e) {
+        *out = profile_of_config(e->cfg);
+        return;
+    }
+    ewk_config c;
+    ewk_default_config(&c);
+    *out = profile_of_config(c);
+}
+
+// ewk_create's tests of the same fields, written so that a NaN fails them too
+static int check_profile(int32_t i, const ewk_detector_profile& p) {
+    const std::string who = "profiles[" + std::to_string(i) + "].";
+    if (!(p.pre_speech_silence > 0)) return fail(EWK_EINVAL, who + "pre_speech_silence must be positive");
+    if (!(p.speech_duration_min > 0)) return fail(EWK_EINVAL, who + "speech_duration_min must be positive");
+    if (!(p.speech_duration_max > 0)) return fail(EWK_EINVAL, who + "speech_duration_max must be positive");
+    if (!(p.speech_duration_min <= p.speech_duration_max))
+        return fail(EWK_EINVAL, who + "speech_duration_min must be <= speech_duration_max");
+    if (!(p.post_speech_silence > 0)) return fail(EWK_EINVAL, who + "post_speech_silence must be positive");
+    if (!(p.padding >= 0)) return fail(EWK_EINVAL, who + "padding must be >= 0");
+    if (!(p.max_segment_seconds > 0)) return fail(EWK_EINVAL, who + "max_segment_seconds must be positive");
+    if (!(p.reentry_timeout == p.reentry_timeout)) return fail(EWK_EINVAL, who + "reentry_timeout is NaN");
+    return EWK_OK;
+}
+
+int ewk_detector_profiles_set(ewk_engine* e, const ewk_detector_profile* profiles, int32_t n) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (e->n_streams <= 0) return fail(EWK_EINVAL, "engine has no streams");
+    if (!profiles) n = 0;
+    if (n < 0 || n > EWK_PROFILE_MAX)
+        return fail(EWK_EINVAL, "a profile table holds 0.." + std::to_string(EWK_PROFILE_MAX) + " profiles, got " +
+                                    std::to_string(n));
+    const ewk_config& c = e->cfg;
+    int64_t need = segment_need(c, e->ring_len, c.speech_duration_max, c.post_speech_silence, c.padding);
+    for (int32_t i = 0; i < n; ++i) {
+        int rc = check_profile(i, profiles[i]);
+        if (rc) return rc;
+        const int64_t ni = segment_need(c, e->ring_len, profiles[i].speech_duration_max,
+                                        profiles[i].post_speech_silence, profiles[i].padding);
+        if (e->sring_len < e->ring_len && e->sring_len < ni + c.block)
+            return fail(EWK_EINVAL, "profiles[" + std::to_string(i) + "]: ring_samples must hold the longest segment "
+                                    "request plus one tick (" + std::to_string(ni + c.block) +
+                                    " samples for this profile, the ring holds " + std::to_string(e->sring_len) + ")");
+        need = std::max(need, ni);
+    }
+    if (n > 0)
+        for (int32_t s = 0; s < (int32_t)e->stream_profile.size(); ++s)
+            if (e->stream_profile[s] >= n)
+                return fail(EWK_EINVAL, "stream " + std::to_string(s) + " points at profile " +
+                                            std::to_string(e->stream_profile[s]) + " of a table of " + std::to_string(n) +
+                                            ": assign it first (ewk_stream_profile_assign), or clear the table");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));    // the pushes so far keep their timings
+    HIP_TRY(hipStreamSynchronize(e->sstream));
+    if (n == 0) {   // table off: every stream back to the engine's configuration
+        if (e->d_stream_profile.p) {
+            HIP_TRY(hipMemset(e->d_stream_profile.p, 0xff, (size_t)e->n_streams * sizeof(int32_t)));
+            std::fill(e->stream_profile.begin(), e->stream_profile.end(), -1);
+        }
+        e->profiles.clear();
+        set_launch_ticks(e, need);   // (the configuration's own again)
+        return EWK_OK;
+    }
+    HIP_TRY(e->d_profiles.reserve((size_t)n));
+    if (!e->d_stream_profile.p) {
+        HIP_TRY(e->d_stream_profile.reserve((size_t)e->n_streams));
+        HIP_TRY(hipMemset(e->d_stream_profile.p, 0xff, (size_t)e->n_streams * sizeof(int32_t)));
+        e->stream_profile.assign((size_t)e->n_streams, -1);
+    }
+    HIP_TRY(hipMemcpy(e->d_profiles.p, profiles, (size_t)n * sizeof(ewk_detector_profile), hipMemcpyHostToDevice));
+    e->profiles.assign(profiles, profiles + n);
+    set_launch_ticks(e, need);
+    return EWK_OK;
+}
+
+int ewk_detector_profiles_info(ewk_engine* e, int32_t* n_profiles) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (n_profiles) *n_profiles = (int32_t)e->profiles.size();
+    return EWK_OK;
+}
+
+int ewk_detector_profile_get(ewk_engine* e, int32_t profile, ewk_detector_profile* out) {
+    if (!e || !out) return fail(EWK_EINVAL, "NULL argument");
+    const int32_t n = (int32_t)e->profiles.size();
+    if (profile < -1 || profile >= n)
+        return fail(EWK_EINVAL, "profile index " + std::to_string(profile) + " is outside [-1, " + std::to_string(n) + ")");
+    *out = profile < 0 ? profile_of_config(e->cfg) : e->profiles[profile];
+    return EWK_OK;
+}
+
+int ewk_stream_profile_assign(ewk_engine* e, const int32_t* streams, int32_t n, const int32_t* profiles) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (e->n_streams <= 0) return fail(EWK_EINVAL, "engine has no streams");
+    if (e->profiles.empty()) return fail(EWK_EINVAL, "no profile table is set (ewk_detector_profiles_set)");
+    int rc = check_stream_list(e, streams, n);
+    if (rc) return rc;
+    if (!profiles) return fail(EWK_EINVAL, "profiles is NULL");
+    const int32_t n_prof = (int32_t)e->profiles.size();
+    for (int32_t i = 0; i < n; ++i)
+        if (profiles[i] < -1 || profiles[i] >= n_prof)
+            return fail(EWK_EINVAL, "profile index " + std::to_string(profiles[i]) + " of stream " +
+                                        std::to_string(streams[i]) + " is outside [-1, " + std::to_string(n_prof) + ")");
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = e->stream;   // (the gate is the only reader, and it runs on s)
+    const int32_t *d_list = nullptr, *d_vals = nullptr;
+    rc = stage_stream_list(e, streams, profiles, n, s, &d_list, &d_vals);
+    if (rc) return rc;
+    HIP_TRY(launch_scatter_i32(e->d_stream_profile.p, d_list, d_vals, n, s));
+    for (int32_t i = 0; i < n; ++i) e->stream_profile[streams[i]] = profiles[i];
+    return EWK_OK;
+}
+
+int ewk_stream_profiles(ewk_engine* e, const int32_t* streams, int32_t n, int32_t* out) {
+    if (!e || !out) return fail(EWK_EINVAL, "NULL argument");
+    if (n < 0 || n > e->n_streams)
+        return fail(EWK_EINVAL, "n must be in [0, " + std::to_string(e->n_streams) + "]");
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t s = streams ? streams[i] : i;
+        if (s < 0 || s >= e->n_streams) return fail_stream_index(e, i, s);
+    }
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t s = streams ? streams[i] : i;
+        out[i] = e->stream_profile.empty() ? -1 : e->stream_profile[s];
+    }
     return EWK_OK;
 }
 

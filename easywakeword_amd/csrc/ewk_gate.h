@@ -93,9 +93,16 @@ struct GateArgs {
     const int32_t* ids;
     int32_t own_clock;        // 1: every stream counts from its own GateStream::tick (tick0 unused)
     int32_t pad1;
+    // Detector profiles (ewk_detector_profiles_set): stream s is gated with the seven timings of
+    // profiles[stream_profile[s]], or with the ones above when the index is -1.  Both nullptr
+    // without a table: launch_gate then picks the instantiations without the profile code.
+    const ewk_detector_profile* profiles;
+    const int32_t* stream_profile;   // [n_streams of the engine], by stream (not by row)
 };
 
-hipError_t launch_gate(const GateArgs& g, hipStream_t s);
+// grid_cap > 0: at most that many workgroups (ewk_create's EWK_GATE_GRID_MAX), below the
+// compile-time maximum; a wave then takes more than one row from 4 * grid_cap rows on.
+hipError_t launch_gate(const GateArgs& g, hipStream_t s, int grid_cap = 0);
 // ewk_reset_stream_list: streams ids[0..n) back to the state ewk_reset_streams gives every stream,
 // in one launch: ring row zeroed with k_ring_zero's agent-scope stores, block RMS row zeroed,
 // GateStream = init, and with a resampler its history row zeroed and its fresh flag set.

@@ -479,7 +479,9 @@ __device__ __forceinline__ double reg_percentile25(const double (&so)[RB], int n
 // whole launch (RB slots per lane, n_blocks <= 64 * RB): loaded once, updated with
 // wave shuffles, stored once -- no dependent global round trips per tick.  RB = 0:
 // both stay in global memory (any n_blocks).
-template <int RB, int DMA>
+// PROF (detector profiles): the stream's seven gate timings come from its profile; without it
+// they are the launch's (GateArgs) and the kernel holds no profile code.
+template <int RB, int DMA, bool PROF = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGateWavesPerEU, 8))) void k_gate_ticks(GateArgs g) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -579,6 +581,26 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGateWavesP
     float* ring = g.ring ? g.ring + (int64_t)s * Rs : nullptr;
     int16_t* ring16 = g.ring16 ? g.ring16 + (int64_t)s * Rs : nullptr;   // PCM16 pushes only (host-checked)
     GateStream st = g.st[s];
+    // The stream's detector timings.  PROF: the profile is looked up again for every stream of
+    // the loop.  s is wave-uniform (readfirstlane) and both arrays are read through the constant
+    // address space -- no kernel writes the table, and the index array only between gate launches
+    // (k_scatter_i32) -- so the index and the doubles behind it are s_load instructions into
+    // SGPRs.  Index -1 (pf null): the engine's configuration, from the launch arguments.  The
+    // re-entry timeout is tested at every tick and kept in registers; the other six are read
+    // where the FSM uses them (a state transition, the cut), so they hold no registers across
+    // the tick's sums.
+    typedef const ewk_detector_profile __attribute__((address_space(4))) * ProfilePtr;
+    typedef const int32_t __attribute__((address_space(4))) * IndexPtr;
+    ProfilePtr pf = nullptr;
+    double reentry_timeout = g.reentry_timeout;
+    if constexpr (PROF) {
+        const int pi = __builtin_amdgcn_readfirstlane(((IndexPtr)g.stream_profile)[s]);
+        if (pi >= 0) {
+            pf = (ProfilePtr)g.profiles + pi;
+            reentry_timeout = pf->reentry_timeout;
+        }
+    }
+#define EWK_GATE_TIMING(field) ((PROF && pf) ? pf->field : g.field)
     const int64_t tick0 = g.own_clock ? st.tick : g.tick0;   // the stream's own clock, or the engine's (equal in lockstep)
     double* grms = g.block_rms + (int64_t)s * nb;
     double* sorted2 = g.sorted_rms + (int64_t)s * 2 * nb;
@@ -602,7 +624,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGateWavesP
         const int64_t tick = tick0 + t + 1;                      // tick being delivered
         const double t_prev = (double)(tick - 1) * g.tick_seconds;
         // start()-mode re-entry (TimeoutError -> _detect_word again), before the sleep
-        if (st.started && g.reentry_timeout > 0.0 && t_prev - st.start_time > g.reentry_timeout) {
+        if (st.started && reentry_timeout > 0.0 && t_prev - st.start_time > reentry_timeout) {
             st.state = kWaiting;
             st.start_time = t_prev;
             if (st.last_silent) { st.state = kInSilence; st.silence_start = t_prev; }
@@ -852,16 +874,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGateWavesP
                 break;
             case kInSilence:
                 if (!silent) {
-                    if (now - st.silence_start >= g.pre_speech_silence) { st.state = kInSound; st.sound_start = now; }
+                    if (now - st.silence_start >= EWK_GATE_TIMING(pre_speech_silence)) { st.state = kInSound; st.sound_start = now; }
                     else st.state = kWaiting;
                 }
                 break;
             case kInSound: {
                 const double d = now - st.sound_start;
                 if (!silent) {
-                    if (d > g.speech_duration_max) st.state = kWaiting;
+                    if (d > EWK_GATE_TIMING(speech_duration_max)) st.state = kWaiting;
                 } else {
-                    if (g.speech_duration_min <= d && d <= g.speech_duration_max) {
+                    if (EWK_GATE_TIMING(speech_duration_min) <= d && d <= EWK_GATE_TIMING(speech_duration_max)) {
                         st.state = kAfterSound;
                         st.sound_end = now;
                     } else st.state = kWaiting;
@@ -870,9 +892,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGateWavesP
             }
             case kAfterSound:
                 if (silent) {
-                    if (now - st.sound_end >= g.post_speech_silence) {
-                        const double xs = st.sound_start - now - g.padding;
-                        const double xe = st.sound_end - now + g.padding;
+                    if (now - st.sound_end >= EWK_GATE_TIMING(post_speech_silence)) {
+                        const double xs = st.sound_start - now - EWK_GATE_TIMING(padding);
+                        const double xe = st.sound_end - now + EWK_GATE_TIMING(padding);
                         int64_t nreq = (int64_t)(fabs(xs) * (double)g.sample_rate);
                         if (nreq > R) nreq = R;
                         const int64_t e = (int64_t)(fabs(xe) * (double)g.sample_rate);
@@ -890,7 +912,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGateWavesP
                         ev.time = now;
                         ev.score = __builtin_nan("");
                         ev.match = 0;
-                        ev.flags = ((double)stop / (double)g.sample_rate > g.max_segment_seconds) ? EWK_EV_SKIPPED : 0;
+                        ev.flags = ((double)stop / (double)g.sample_rate > EWK_GATE_TIMING(max_segment_seconds)) ? EWK_EV_SKIPPED : 0;
                         if (lane == 0) {
                             const uint32_t slot = (uint32_t)atomicAdd(g.ev_count, 1) - (uint32_t)g.ev_base0;
                             if (slot < (uint32_t)g.ev_cap) g.events[slot] = ev;
@@ -918,6 +940,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGateWavesP
     if (DMA == 3) load_vec(r, 0);
     else if (!dma) load_chunk(0, 0);
     }
+#undef EWK_GATE_TIMING
 }
 
 // _detect_word entry (wakeword.py:1048-1057) for streams whose detection runs: state from
@@ -1020,10 +1043,11 @@ int gate_val_len(const PwTree* trees_host, int n_blocks) {
     return std::max(2, (m + 1) & ~1);
 }
 
-hipError_t launch_gate(const GateArgs& g, hipStream_t s) {
+hipError_t launch_gate(const GateArgs& g, hipStream_t s, int grid_cap) {
     if (g.n_streams <= 0 || g.n_ticks <= 0) return hipSuccess;
     // one wave per stream (the hardware refills freed slots), up to kGateGridMax workgroups
-    const int grid = std::min((g.n_streams + 3) / 4, kGateGridMax);
+    const int grid = std::min((g.n_streams + 3) / 4, grid_cap > 0 ? std::min(grid_cap, kGateGridMax) : kGateGridMax);
+    if ((g.profiles == nullptr) != (g.stream_profile == nullptr)) return hipErrorInvalidValue;
     // (the int16 vector path stages int16; every other path float)
     const int64_t nl = std::min<int64_t>(g.n_last, g.ring_len);
     const bool dma = g.pcm16 == nullptr && g.stage >= g.block && g.stage >= nl;
@@ -1039,6 +1063,22 @@ hipError_t launch_gate(const GateArgs& g, hipStream_t s) {
     const bool i16stage = vec16 && !dma4 && g.n_blocks <= 64 * kGateRegMax;
     const size_t lds = 4 * gate_wave_lds(g.val_len, g.stage, i16stage ? 2 : 4) +
                        2 * sizeof(PwTree);   // + the two sub-chunk trees (k_gate_ticks)
+    if (g.profiles) {   // the same families with the per-stream timings
+        if (g.n_blocks <= 128) {
+            if (dma4) hipLaunchKernelGGL((k_gate_ticks<2, 2, true>), dim3(grid), dim3(256), lds, s, g);
+            else if (vec16) hipLaunchKernelGGL((k_gate_ticks<2, 3, true>), dim3(grid), dim3(256), lds, s, g);
+            else if (dma) hipLaunchKernelGGL((k_gate_ticks<2, 1, true>), dim3(grid), dim3(256), lds, s, g);
+            else hipLaunchKernelGGL((k_gate_ticks<2, 0, true>), dim3(grid), dim3(256), lds, s, g);
+        } else if (g.n_blocks <= 64 * kGateRegMax) {
+            if (dma4) hipLaunchKernelGGL((k_gate_ticks<kGateRegMax, 2, true>), dim3(grid), dim3(256), lds, s, g);
+            else if (vec16) hipLaunchKernelGGL((k_gate_ticks<kGateRegMax, 3, true>), dim3(grid), dim3(256), lds, s, g);
+            else if (dma) hipLaunchKernelGGL((k_gate_ticks<kGateRegMax, 1, true>), dim3(grid), dim3(256), lds, s, g);
+            else hipLaunchKernelGGL((k_gate_ticks<kGateRegMax, 0, true>), dim3(grid), dim3(256), lds, s, g);
+        } else {
+            hipLaunchKernelGGL((k_gate_ticks<0, 0, true>), dim3(grid), dim3(256), lds, s, g);
+        }
+        return hipGetLastError();
+    }
     if (g.n_blocks <= 128) {
         if (dma4) hipLaunchKernelGGL((k_gate_ticks<2, 2>), dim3(grid), dim3(256), lds, s, g);
         else if (vec16) hipLaunchKernelGGL((k_gate_ticks<2, 3>), dim3(grid), dim3(256), lds, s, g);

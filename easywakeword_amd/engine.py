@@ -9,6 +9,7 @@ No CPU fallback exists: construction raises when libewk.so or a GPU is missing.
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import asdict, dataclass
 from typing import Optional, Tuple
 
 import numpy as np
@@ -35,6 +36,19 @@ def _pack(segs):
         offsets[1:] = np.cumsum(lengths[:-1], dtype=np.int64)
     pcm = np.ascontiguousarray(np.concatenate(segs) if n else np.zeros(0, np.float32), dtype=np.float32)
     return pcm, offsets, lengths
+
+
+@dataclass
+class DetectorProfile:
+    """The level-1 timings one WakeWord owns (include/ewk.h, ewk_detector_profile): an entry of
+    StreamEngine.set_detector_profiles.  A field left None takes the engine's configuration."""
+    pre_speech_silence: Optional[float] = None
+    speech_duration_min: Optional[float] = None
+    speech_duration_max: Optional[float] = None
+    post_speech_silence: Optional[float] = None
+    padding: Optional[float] = None
+    max_segment_seconds: Optional[float] = None
+    reentry_timeout: Optional[float] = None    # <= 0: continuous; > 0: start()-mode re-entry
 
 
 def bank_layout(words, thresholds=None):
@@ -550,6 +564,72 @@ class StreamEngine(Engine):
         if w.size != s.size:
             raise ValueError(f"{w.size} word indices for {s.size} streams")
         check(self._lib.ewk_stream_bank_assign(self._h, _lib.i32ptr(s), s.size, _lib.i32ptr(w)))
+
+    # -- detector profiles: per-stream gate timings ---------------------------------
+    def _profile_struct(self, i: int, p, base: _lib.EwkDetectorProfile) -> _lib.EwkDetectorProfile:
+        d = asdict(p) if isinstance(p, DetectorProfile) else dict(p)
+        out = _lib.EwkDetectorProfile()
+        for f in _lib.PROFILE_FIELDS:
+            v = d.pop(f, None)
+            setattr(out, f, float(getattr(base, f) if v is None else v))
+        if d:
+            raise TypeError(f"profiles[{i}]: unknown field(s) {sorted(d)}")
+        return out
+
+    def set_detector_profiles(self, profiles) -> None:
+        """The table of detector profiles: a sequence of DetectorProfile instances or dicts of
+        their fields (pre_speech_silence, speech_duration_min, speech_duration_max,
+        post_speech_silence, padding, max_segment_seconds, reentry_timeout); a missing field takes
+        the engine's configuration.  Streams choose an entry with assign_stream_profiles; until
+        then, and on index -1, a stream is gated with the engine's configuration as before.
+        None or []: table off, every stream back to -1.  Waits for the pushes so far.  ValueError
+        (nothing changes) names the entry and field of a bad value, a profile whose longest segment
+        does not fit a compact ring, or a stream still pointing past a shorter table."""
+        profiles = list(profiles) if profiles is not None else []
+        if not profiles:
+            check(self._lib.ewk_detector_profiles_set(self._h, None, 0))
+            return
+        base = _lib.EwkDetectorProfile()
+        self._lib.ewk_default_detector_profile(self._h, C.byref(base))
+        arr = (_lib.EwkDetectorProfile * len(profiles))(
+            *[self._profile_struct(i, p, base) for i, p in enumerate(profiles)])
+        check(self._lib.ewk_detector_profiles_set(self._h, arr, len(profiles)))
+
+    def detector_profiles(self) -> list:
+        """The table as set: a list of DetectorProfile (empty without a table)."""
+        n = C.c_int32(0)
+        check(self._lib.ewk_detector_profiles_info(self._h, C.byref(n)))
+        out = []
+        for i in range(int(n.value)):
+            p = _lib.EwkDetectorProfile()
+            check(self._lib.ewk_detector_profile_get(self._h, i, C.byref(p)))
+            out.append(DetectorProfile(**{f: float(getattr(p, f)) for f in _lib.PROFILE_FIELDS}))
+        return out
+
+    def assign_stream_profiles(self, streams, profiles) -> None:
+        """Stream streams[i] is gated with entry profiles[i] of the table (-1: the engine's
+        configuration) from the next push on.  Its FSM state and clock are kept; stream-ordered,
+        no wait.  ValueError (nothing changes) for an index outside [-1, len(table)), a stream out
+        of range or listed twice, or without a table."""
+        s = self._stream_list(streams)
+        p = np.ascontiguousarray(profiles, dtype=np.int32).reshape(-1)
+        if p.size != s.size:
+            raise ValueError(f"{p.size} profile indices for {s.size} streams")
+        check(self._lib.ewk_stream_profile_assign(self._h, _lib.i32ptr(s), s.size, _lib.i32ptr(p)))
+
+    def stream_profiles(self, streams=None) -> np.ndarray:
+        """The profile index of each listed stream (None: all), -1 = the engine's configuration
+        (int32; host bookkeeping, no wait)."""
+        if streams is None:
+            out = np.zeros(self.n_streams, np.int32)
+            check(self._lib.ewk_stream_profiles(self._h, None, self.n_streams, _lib.i32ptr(out)))
+            return out
+        s = np.ascontiguousarray(streams, dtype=np.int32).reshape(-1)
+        if s.size > self.n_streams:
+            raise ValueError(f"{s.size} streams listed, the engine has {self.n_streams}")
+        out = np.zeros(s.size, np.int32)
+        check(self._lib.ewk_stream_profiles(self._h, _lib.i32ptr(s), s.size, _lib.i32ptr(out)))
+        return out
 
     # -- stream bank: gated events against many references, per stream ------------
     def set_stream_bank(self, stream_word=None) -> None:

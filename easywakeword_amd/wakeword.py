@@ -253,6 +253,81 @@ def normalize_for_transcription(audio_samples: np.ndarray, engine=None) -> np.nd
     return eng.normalize([np.asarray(audio_samples)])[0]
 
 
+def analyze_reference_audio_duration(wavword, log=None) -> Optional[float]:
+    """WakeWord._analyze_reference_audio_duration on a WAV path: the RMS voice-activity duration
+    in seconds (at least 0.2), None when the file cannot be analysed (logged through `log`)."""
+    try:
+        audio = _audio.load_wav(wavword)
+        frame_length, hop_length = int(0.025 * FREQUENCY), int(0.010 * FREQUENCY)
+        pad = np.pad(audio, (frame_length // 2, frame_length // 2), mode="constant")
+        T = 1 + (len(pad) - frame_length) // hop_length
+        idx = np.arange(T)[:, None] * hop_length + np.arange(frame_length)[None, :]
+        rms = np.sqrt(np.mean(np.abs(pad[idx].T) ** 2, axis=-2))
+        threshold = np.max(rms) * VOICE_ACTIVITY_THRESHOLD
+        voice = np.where(rms > threshold)[0]
+        if voice.size:
+            duration = (voice[-1] - voice[0]) * hop_length / FREQUENCY
+            return max(duration, MIN_DETECTED_DURATION)
+    except Exception as e:  # noqa: BLE001 - reference swallows and logs
+        if log is not None:
+            log(f"Could not analyze reference audio duration: {e}", logging.WARNING)
+    return None
+
+
+def auto_speech_durations(user_min, user_max, analyze) -> Tuple[float, float]:
+    """WakeWord._auto_calculate_speech_durations: (speech_duration_min, speech_duration_max) from
+    the user's values (None: automatic) and `analyze()`, the analysed reference duration or None."""
+    d = None   # the WAV is analysed once, and only when a default needs it
+    if user_min is not None:
+        smin = float(user_min)
+    else:
+        d = analyze()
+        smin = float(d) if d is not None else DEFAULT_SPEECH_DURATION_MIN
+    if user_max is not None:
+        smax = float(user_max)
+    elif user_min is None and d is None:   # no duration in the WAV: both fallbacks
+        smax = DEFAULT_SPEECH_DURATION_MAX
+    else:
+        smax = 2.0 * smin
+    if smax < smin:
+        smax = smin
+    return smin, smax
+
+
+def detector_profile(wavword=None, textword=None, *, pre_speech_silence: float = DEFAULT_PRE_SPEECH_SILENCE,
+                     speech_duration_min: Optional[float] = AUTO_CALCULATE,
+                     speech_duration_max: Optional[float] = AUTO_CALCULATE,
+                     post_speech_silence: float = DEFAULT_POST_SPEECH_SILENCE, padding: Optional[float] = None,
+                     max_segment_seconds: Optional[float] = None, reentry_timeout: Optional[float] = None):
+    """The gate timings a WakeWord(textword, wavword, ...) built with the same arguments ends up
+    with, as an engine.DetectorProfile for StreamEngine.set_detector_profiles: the speech durations
+    from the analysed reference recording (the first of several), explicit values winning, the
+    reference defaults otherwise.  padding, max_segment_seconds and reentry_timeout are not WakeWord
+    arguments: None leaves them to the engine's configuration.  textword is accepted for symmetry
+    with WakeWord (the durations never depend on it)."""
+    from .engine import DetectorProfile
+    if pre_speech_silence <= 0:
+        raise ValueError("pre_speech_silence must be positive")
+    if speech_duration_min is not None and speech_duration_min <= 0:
+        raise ValueError("speech_duration_min must be positive")
+    if speech_duration_max is not None and speech_duration_max <= 0:
+        raise ValueError("speech_duration_max must be positive")
+    if (speech_duration_min is not None and speech_duration_max is not None
+            and speech_duration_min > speech_duration_max):
+        raise ValueError("speech_duration_min must be <= speech_duration_max")
+    if post_speech_silence <= 0:
+        raise ValueError("post_speech_silence must be positive")
+    if wavword is not None and not (isinstance(wavword, (str, bytes)) or hasattr(wavword, "__fspath__")):
+        wavword = list(wavword)[0]
+    smin, smax = auto_speech_durations(
+        speech_duration_min, speech_duration_max,
+        lambda: analyze_reference_audio_duration(wavword) if wavword is not None else None)
+    return DetectorProfile(pre_speech_silence=float(pre_speech_silence), speech_duration_min=smin,
+                           speech_duration_max=smax, post_speech_silence=float(post_speech_silence),
+                           padding=padding, max_segment_seconds=max_segment_seconds,
+                           reentry_timeout=reentry_timeout)
+
+
 class WakeWord:
     """Wake word detector (reference wakeword.py:642-1240) on the MI355X engine.
 
@@ -358,45 +433,16 @@ class WakeWord:
         """RMS voice-activity duration of the reference WAV (wakeword.py:854-898):
         librosa.feature.rms(frame 400, hop 160, centred, zero pad) > 0.1 x max,
         (last - first) * 160 / 16000, at least 0.2 s."""
-        try:
-            audio = _audio.load_wav(self.wavword)
-            frame_length, hop_length = int(0.025 * FREQUENCY), int(0.010 * FREQUENCY)
-            pad = np.pad(audio, (frame_length // 2, frame_length // 2), mode="constant")
-            T = 1 + (len(pad) - frame_length) // hop_length
-            idx = np.arange(T)[:, None] * hop_length + np.arange(frame_length)[None, :]
-            rms = np.sqrt(np.mean(np.abs(pad[idx].T) ** 2, axis=-2))
-            threshold = np.max(rms) * VOICE_ACTIVITY_THRESHOLD
-            voice = np.where(rms > threshold)[0]
-            if voice.size:
-                duration = (voice[-1] - voice[0]) * hop_length / FREQUENCY
-                return max(duration, MIN_DETECTED_DURATION)
-        except Exception as e:  # noqa: BLE001 - reference swallows and logs
-            self._log(f"Could not analyze reference audio duration: {e}", logging.WARNING)
-        return None
+        return analyze_reference_audio_duration(self.wavword, self._log)
 
     def _auto_calculate_speech_durations(self) -> None:
         """Called by the reference constructor (wakeword.py:786) but missing from
         the snapshot; behaviour pinned by tests/test_wakeword_simulated.py:687-775:
         min = analysed WAV speech duration (fallback 0.3), max = 2 x min unless the
         user gave one (fallback 2.0)."""
-        user_min = getattr(self, "_user_speech_duration_min", None)
-        user_max = getattr(self, "_user_speech_duration_max", None)
-        d = None   # the WAV is analysed once, and only when a default needs it
-        if user_min is not None:
-            smin = float(user_min)
-        else:
-            d = self._analyze_reference_audio_duration()
-            smin = float(d) if d is not None else DEFAULT_SPEECH_DURATION_MIN
-        if user_max is not None:
-            smax = float(user_max)
-        elif user_min is None and d is None:   # no duration in the WAV: both fallbacks
-            smax = DEFAULT_SPEECH_DURATION_MAX
-        else:
-            smax = 2.0 * smin
-        if smax < smin:
-            smax = smin
-        self.speech_duration_min = smin
-        self.speech_duration_max = smax
+        self.speech_duration_min, self.speech_duration_max = auto_speech_durations(
+            getattr(self, "_user_speech_duration_min", None), getattr(self, "_user_speech_duration_max", None),
+            self._analyze_reference_audio_duration)
 
     def _set_thresholds_from_audio_duration(self, audio_duration: float) -> None:
         if getattr(self, "pre_speech_silence", None) is None:

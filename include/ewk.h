@@ -145,7 +145,10 @@ int ewk_device_count(void);
  * never in use at once. */
 int ewk_runtime_info(char* path, int32_t cap, int32_t* hip_version);
 
-/* Engine: device index, number of concurrent streams (0 = scorer only). */
+/* Engine: device index, number of concurrent streams (0 = scorer only).  Read from the environment
+ * at creation: EWK_SCORE_OVERLAP=1 (score tick t beside the gate of tick t + 1) and
+ * EWK_GATE_GRID_MAX=<positive integer> (at most that many workgroups per gate launch, below the
+ * built-in 131,072: a wave then steps several streams in turn; same results, for tests). */
 int ewk_create(ewk_engine** out, int device, int32_t n_streams, const ewk_config* cfg);
 void ewk_destroy(ewk_engine* e);
 int ewk_sync(ewk_engine* e);
@@ -345,6 +348,61 @@ int ewk_stream_bank_disable(ewk_engine* e);   /* back to the single template; no
  * EWK_EINVAL when the stream bank is off, for a stream out of range or listed twice, or a word
  * outside [0, n_words); nothing changes then. */
 int ewk_stream_bank_assign(ewk_engine* e, const int32_t* streams, int32_t n, const int32_t* words);
+
+/* ---- level 1 per word: detector profiles ------------------------------------------ */
+/* In the reference every WakeWord owns its gate timings: the four durations derived from its
+ * reference recording (_auto_calculate_speech_durations, wakeword.py:827-943) and its start()-mode
+ * re-entry timeout.  A detector profile is those per-WakeWord fields of ewk_config; an engine
+ * holds a table of 0..EWK_PROFILE_MAX profiles and every stream points at one of them, the way
+ * it points at a word of the stream bank.
+ *
+ * Profile index.  -1 is the engine's own configuration, exactly as without a table -- including
+ * whatever ewk_reenter last stored as its re-entry timeout.  Every stream starts at -1, and a
+ * stream on -1 behaves bit for bit as before whether or not a table exists.  Indices 0..n-1 are
+ * the table's entries.  The gate re-reads the stream's timings at every launch; nothing else of
+ * the stream (block, ring, thresholds, tick_seconds) is per profile.
+ *
+ * Ring safety.  The longest segment request of a profile is int((speech_duration_max +
+ * post_speech_silence + tick_seconds + padding) * sample_rate) + 2 samples (capped at the
+ * reference ring).  A compact ring (ewk_config.ring_samples) must hold that plus one block for
+ * every profile of the table, and the number of ticks per gate launch (ewk_push_many) follows the
+ * largest request over the engine's configuration and the table; it returns to the engine's own
+ * when the table is cleared. */
+#define EWK_PROFILE_MAX 65536
+typedef struct ewk_detector_profile {   /* 56 bytes; the per-WakeWord fields of ewk_config */
+    double pre_speech_silence, speech_duration_min, speech_duration_max, post_speech_silence;
+    double padding, max_segment_seconds;
+    double reentry_timeout;             /* <= 0: continuous; > 0: start()-mode re-entry */
+} ewk_detector_profile;
+/* The engine's configuration as a profile (what index -1 means; e NULL: the reference defaults
+ * of ewk_default_config). */
+void ewk_default_detector_profile(const ewk_engine* e_or_null, ewk_detector_profile* out);
+/* Replace the table (host array, copied).  n = 0 or profiles NULL: table off, every stream back
+ * to -1.  Every entry is validated as ewk_create validates the same fields: the four durations
+ * positive, speech_duration_min <= speech_duration_max, padding >= 0, max_segment_seconds > 0,
+ * no NaN, n <= EWK_PROFILE_MAX, and with a compact ring the request above plus one block within
+ * ring_samples -- else EWK_EINVAL naming the entry and the field (or the samples needed), and
+ * nothing changes.  Replacing a table while a stream points at an index >= n is refused
+ * (EWK_EINVAL): assign those streams first, or clear the table.  EWK_EINVAL for an engine without
+ * streams.  Waits for the pushes so far.  The first table allocates the per-stream index (4 bytes
+ * per stream on the device, 4 on the host), freed with the engine. */
+int ewk_detector_profiles_set(ewk_engine* e, const ewk_detector_profile* profiles, int32_t n);
+/* 0 without a table. */
+int ewk_detector_profiles_info(ewk_engine* e, int32_t* n_profiles);
+/* Entry `profile` of the table; -1: the engine's configuration (ewk_default_detector_profile). */
+int ewk_detector_profile_get(ewk_engine* e, int32_t profile, ewk_detector_profile* out);
+/* Stream streams[i] is gated with profile profiles[i] (-1: the engine's configuration) from the
+ * next push on.  Host arrays, `streams` as for ewk_push_streams (validated before anything is
+ * enqueued, no duplicates); every profile in [-1, n_profiles), else EWK_EINVAL and nothing
+ * changes.  Stream-ordered behind the pushes so far, no host wait.  The stream's FSM state and
+ * clock are not touched: the next tick steps the same state with the new numbers, as the
+ * reference would if the attributes of a live WakeWord were changed between two polls.  A lockstep
+ * engine stays in lockstep.  ewk_reset_streams and ewk_reset_stream_list keep the assignments, as
+ * they keep word assignments: a reused slot calls this. */
+int ewk_stream_profile_assign(ewk_engine* e, const int32_t* streams, int32_t n, const int32_t* profiles);
+/* The profile of each listed stream (streams NULL: streams 0..n-1); all -1 without a table.
+ * Host mirror: no device access, no wait. */
+int ewk_stream_profiles(ewk_engine* e, const int32_t* streams, int32_t n, int32_t* out);
 
 /* ---- either side of the path --------------------------------------- */
 /* Level-3 input: WakeWord._transcribe_audio's normalisation (wakeword.py:1019-1025)
