@@ -5,13 +5,13 @@ Drop-in for the hot path of raymondclowe/EasyWakeWord: the level-1 energy gate
 MFCC + cosine matcher, as hand-written HIP kernels behind a C ABI
 (include/ewk.h, libewk.so) bound with ctypes.
 
-    from easywakeword_amd import WakeWord, WordMatcher, StreamEngine
+    from easywakeword_amd import WakeWord, WakeWordSet, WordMatcher, StreamEngine
 """
 from .engine import DetectorProfile, Engine, StreamEngine
-from .wakeword import SoundBuffer, WakeWord, WordMatcher, detector_profile
+from .wakeword import SoundBuffer, WakeWord, WakeWordSet, WordMatcher, detector_profile
 from .audio import ArraySource, WavSource, load_wav, write_wav
 from .devices import AudioDeviceManager
 
-__all__ = ["WakeWord", "WordMatcher", "SoundBuffer", "Engine", "StreamEngine", "DetectorProfile", "detector_profile",
+__all__ = ["WakeWord", "WakeWordSet", "WordMatcher", "SoundBuffer", "Engine", "StreamEngine", "DetectorProfile", "detector_profile",
            "ArraySource", "WavSource", "load_wav", "write_wav", "AudioDeviceManager"]
 __version__ = "0.1.0"

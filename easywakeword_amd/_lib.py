@@ -45,6 +45,8 @@ EWK_COMPACT_APPEND = 1
 EWK_BANK_MAX_PER_WORD = 64
 EWK_BANK_MAX_TEMPLATES = 65536
 EWK_PROFILE_MAX = 65536
+EWK_LISTENERS_MAX = 16       # listeners (detector profile, word) per stream
+EWK_EV_LISTENER_SHIFT = 16   # bits 16..19 of an event's flags: the listener that cut it
 
 # Every symbol include/ewk.h declares (checked by tests/test_capi.py).
 EXPORTS = [
@@ -65,6 +67,7 @@ EXPORTS = [
     "ewk_stream_bank_assign",
     "ewk_default_detector_profile", "ewk_detector_profiles_set", "ewk_detector_profiles_info",
     "ewk_detector_profile_get", "ewk_stream_profile_assign", "ewk_stream_profiles",
+    "ewk_stream_listeners_set", "ewk_stream_listeners", "ewk_get_listener_state",
 ]
 
 
@@ -87,6 +90,11 @@ class EwkDetectorProfile(C.Structure):
         ("post_speech_silence", C.c_double), ("padding", C.c_double), ("max_segment_seconds", C.c_double),
         ("reentry_timeout", C.c_double),
     ]
+
+
+class EwkListener(C.Structure):
+    """ewk_listener: a stream's listener, (detector profile or -1, word of the stream bank)."""
+    _fields_ = [("profile", C.c_int32), ("word", C.c_int32)]
 
 
 PROFILE_FIELDS = tuple(f for f, _ in EwkDetectorProfile._fields_)
@@ -226,6 +234,9 @@ def load():
             "ewk_detector_profile_get": (C.c_int, [_P, C.c_int32, C.POINTER(EwkDetectorProfile)]),
             "ewk_stream_profile_assign": (C.c_int, [_P, _i32p, C.c_int32, _i32p]),
             "ewk_stream_profiles": (C.c_int, [_P, _i32p, C.c_int32, _i32p]),
+            "ewk_stream_listeners_set": (C.c_int, [_P, _i32p, C.c_int32, _i32p, C.POINTER(EwkListener), C.c_int32]),
+            "ewk_stream_listeners": (C.c_int, [_P, C.c_int32, C.POINTER(EwkListener), C.c_int32, _i32p]),
+            "ewk_get_listener_state": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(EwkStreamState)]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)
@@ -257,6 +268,12 @@ def event_best_template(flags):
     """The best template's index inside its word (include/ewk.h, EWK_EV_BEST) of an event scored
     against the stream bank (EWK_EV_BANK, non-NaN score); works on an int or an array of flags."""
     return (flags >> EWK_EV_BEST_SHIFT) & 63
+
+
+def event_listener(flags):
+    """The listener that cut an event (include/ewk.h, EWK_EV_LISTENER): 0 for a stream that was
+    never given listeners; works on an int or an array of flags."""
+    return (flags >> EWK_EV_LISTENER_SHIFT) & 15
 
 
 def default_config(**overrides) -> EwkConfig:

@@ -201,7 +201,7 @@ __global__ __launch_bounds__(64 * kBankWaves, 2) void k_bank(BankArgs a) {
 
 // The events of a streaming tick: event slot base + i of the pending window (float32 pass) /
 // slot ev_list[kEvListHdr + i] (fp64 pass).  Statistics are by event slot in both passes.  An
-// event's word is its stream's; a skipped event (EWK_EV_SKIPPED: no level-2 call) is left alone.
+// event's word is its stream's, or its listener's when listener j >= 1 cut it; a skipped event (EWK_EV_SKIPPED: no level-2 call) is left alone.
 template <typename ST>
 struct EventSrc {
     static constexpr bool kRescore = sizeof(ST) == sizeof(double);
@@ -213,7 +213,10 @@ struct EventSrc {
         seg = kRescore ? x.ev_list[kEvListHdr + i] : base + i;
         const ewk_event* ev = s.events + seg;
         len = ev->length;
-        w = (ev->flags & EWK_EV_SKIPPED) ? -1 : (x.stream_word ? x.stream_word[ev->stream] : 0);
+        const int lj = EWK_EV_LISTENER(ev->flags);   // (listener 0's word is the stream's)
+        if (ev->flags & EWK_EV_SKIPPED) w = -1;
+        else if (lj && x.lsn_tab) w = x.lsn_tab[(int64_t)ev->stream * EWK_LISTENERS_MAX + lj].word;
+        else w = x.stream_word ? x.stream_word[ev->stream] : 0;
     }
     __device__ int64_t row(int, int seg) const { return seg; }
     __device__ double* scores(int) const { return nullptr; }

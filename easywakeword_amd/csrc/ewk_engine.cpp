@@ -147,6 +147,8 @@ void ewk_destroy(ewk_engine* e) {
     (void)hipFree(e->d_compact);
     if (e->h_ids) (void)hipHostFree(e->h_ids);
     if (e->h_ids_free) (void)hipEventDestroy(e->h_ids_free);
+    if (e->h_lsn_stage) (void)hipHostFree(e->h_lsn_stage);
+    if (e->h_lsn_free) (void)hipEventDestroy(e->h_lsn_free);
     (void)hipFree(e->d_ring);
     (void)hipFree(e->d_brms);
     (void)hipFree(e->d_sorted);

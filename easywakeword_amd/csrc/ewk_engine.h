@@ -190,7 +190,25 @@ struct ewk_engine {
     ewk::DevBuf<ewk_detector_profile> d_profiles;
     ewk::DevBuf<int32_t> d_stream_profile;    // [n_streams]
     std::vector<int32_t> stream_profile;      // [n_streams]
-    int32_t gate_grid_cap = 0;      // EWK_GATE_GRID_MAX at ewk_create: workgroups per gate launch (0: the built-in maximum)
+    // Stream listeners (ewk_stream_listeners_set).  Allocated by the first call that gives a stream
+    // more than one listener: per stream the count, EWK_LISTENERS_MAX table rows and kLsnStates
+    // states on the device, count and rows mirrored on the host (row 0 of the mirror is not read:
+    // listener 0 is stream_profile[s] and stream_word[s]).  lsn_multi: streams with more than one
+    // listener; the gate runs its listener instantiations only while it is > 0.  lsn_stage: pinned
+    // [n_streams * (1 + 2 * EWK_LISTENERS_MAX)] ints, a call's counts and rows on the way to
+    // d_lsn_stage (the stream list goes through h_ids).
+    ewk::DevBuf<int32_t> d_lsn_count;          // [n_streams]
+    ewk::DevBuf<ewk_listener> d_lsn_tab;       // [n_streams][EWK_LISTENERS_MAX]
+    ewk::DevBuf<ewk::LsnState> d_lsn_st;       // [n_streams][kLsnStates]
+    std::vector<int32_t> lsn_count;            // [n_streams]; empty: every stream has one listener
+    std::vector<ewk_listener> lsn_tab;         // [n_streams][EWK_LISTENERS_MAX]
+    int32_t lsn_multi = 0;
+    int32_t* h_lsn_stage = nullptr;
+    ewk::DevBuf<int32_t> d_lsn_stage;
+    hipEvent_t h_lsn_free = nullptr;           // recorded after the last DMA out of h_lsn_stage
+    std::vector<int32_t> stream_word;          // host mirror of sb_word (empty: word 0 everywhere)
+    bool listeners_on() const { return !lsn_count.empty(); }
+    int32_t gate_grid_cap = 0;     // EWK_GATE_GRID_MAX at ewk_create: workgroups per gate launch (0: the built-in maximum)
     int32_t gate_stage = 0;
     int32_t gate_val_len = 0;       // per-wave LDS doubles of the gate (tree values, sort scratch)
 

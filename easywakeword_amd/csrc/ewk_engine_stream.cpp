@@ -47,6 +47,8 @@ int ewk_reset_streams(ewk_engine* e) {
         x.last_silent = 1;
     }
     HIP_TRY(hipMemcpyAsync(e->d_st, st.data(), st.size() * sizeof(GateStream), hipMemcpyHostToDevice, s));
+    // (the listener table stays, as profile and word assignments stay; the states start again)
+    if (e->d_lsn_st.p) HIP_TRY(hipMemsetAsync(e->d_lsn_st.p, 0, e->d_lsn_st.cap * sizeof(LsnState), s));
     HIP_TRY(hipMemsetAsync(e->d_work, 0, kWorkInts * sizeof(int32_t), s));
     // (a stream bank stays enabled; its list of events to re-score starts empty)
     if (e->sb_list.p) HIP_TRY(hipMemsetAsync(e->sb_list.p, 0, kEvListHdr * sizeof(int32_t), s));
@@ -68,6 +70,15 @@ int ewk_reset_streams(ewk_engine* e) {
 static int fail_stream_index(ewk_engine* e, int32_t i, int32_t s) {
     return fail(EWK_EINVAL, "streams[" + std::to_string(i) + "] = " + std::to_string(s) + " is outside [0, " +
                                 std::to_string(e->n_streams) + ")");
+}
+
+static std::string listener_of(int32_t stream, int32_t j) {
+    return "listener " + std::to_string(j) + " of stream " + std::to_string(stream);
+}
+
+static int fail_listener_word(int32_t stream, int32_t j, int32_t word, int32_t n_words) {
+    return fail(EWK_EINVAL, listener_of(stream, j) + ": word " + std::to_string(word) + " is outside [0, " +
+                                std::to_string(n_words) + ")");
 }
 
 static int check_stream_list(ewk_engine* e, const int32_t* streams, int32_t n) {
@@ -183,6 +194,7 @@ static int score_pending_bank(ewk_engine* e, hipStream_t ss, const int32_t* n_ev
     BankEvArgs x;
     x.stream_word = e->sbank_words ? e->sb_word.p : nullptr;
     x.ev_list = e->sb_list.p;
+    x.lsn_tab = e->d_lsn_tab.p;
     x.grid = stream_bank_grid(e);
     {
         ProfScope ps(e, 0, ss);
@@ -229,6 +241,11 @@ int ewk_stream_bank_enable(ewk_engine* e, const int32_t* stream_word) {
         for (int32_t s = 0; s < e->n_streams; ++s)
             if (stream_word[s] < 0 || stream_word[s] >= n_words)
                 return fail_word_index(stream_word[s], kOfStream, s, n_words);
+    for (int32_t s = 0; s < (int32_t)e->lsn_count.size(); ++s)
+        for (int32_t j = 1; j < e->lsn_count[s]; ++j) {
+            const int32_t w = e->lsn_tab[(size_t)s * EWK_LISTENERS_MAX + j].word;
+            if (w < 0 || w >= n_words) return fail_listener_word(s, j, w, n_words);
+        }
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipStreamSynchronize(e->stream));    // the pushes so far keep their scoring
     HIP_TRY(hipStreamSynchronize(e->sstream));
@@ -245,6 +262,8 @@ int ewk_stream_bank_enable(ewk_engine* e, const int32_t* stream_word) {
         HIP_TRY(e->sb_word.reserve((size_t)e->n_streams));
         HIP_TRY(hipMemcpy(e->sb_word.p, stream_word, (size_t)e->n_streams * sizeof(int32_t), hipMemcpyHostToDevice));
     }
+    if (stream_word) e->stream_word.assign(stream_word, stream_word + e->n_streams);
+    else e->stream_word.clear();
     e->sbank_words = stream_word != nullptr;
     e->sbank_on = true;
     return EWK_OK;
@@ -325,6 +344,12 @@ static GateArgs gate_args(ewk_engine* e) {
     if (!e->profiles.empty()) {   // (else nullptr: the gate without the profile code)
         g.profiles = e->d_profiles.p;
         g.stream_profile = e->d_stream_profile.p;
+    }
+    if (e->lsn_multi > 0) {   // (else nullptr: the gate without the listener code)
+        g.lsn_count = e->d_lsn_count.p;
+        g.lsn_tab = e->d_lsn_tab.p;
+        g.lsn_st = e->d_lsn_st.p;
+        g.stream_profile = e->d_stream_profile.p;   // (all -1 without a table)
     }
     return g;
 }
@@ -480,6 +505,7 @@ int ewk_reset_stream_list(ewk_engine* e, const int32_t* streams, int32_t n) {
         a.H = e->rs_in.H;
         a.fresh = e->rs_flags.p;
     }
+    a.lsn_st = e->d_lsn_st.p;
     HIP_TRY(launch_reset_list(a, s));
     for (int32_t i = 0; i < n; ++i) e->tick_delta[streams[i]] = -e->tick;
     return EWK_OK;
@@ -518,6 +544,8 @@ int ewk_stream_bank_assign(ewk_engine* e, const int32_t* streams, int32_t n, con
     rc = stage_stream_list(e, streams, words, n, s, &d_list, &d_vals);
     if (rc) return rc;
     HIP_TRY(launch_scatter_i32(e->sb_word.p, d_list, d_vals, n, s));
+    if (e->stream_word.empty()) e->stream_word.assign((size_t)e->n_streams, 0);
+    for (int32_t i = 0; i < n; ++i) e->stream_word[streams[i]] = words[i];
     return EWK_OK;
 }
 
@@ -586,6 +614,14 @@ int ewk_detector_profiles_set(ewk_engine* e, const ewk_detector_profile* profile
                 return fail(EWK_EINVAL, "stream " + std::to_string(s) + " points at profile " +
                                             std::to_string(e->stream_profile[s]) + " of a table of " + std::to_string(n) +
                                             ": assign it first (ewk_stream_profile_assign), or clear the table");
+    for (int32_t s = 0; s < (int32_t)e->lsn_count.size(); ++s)
+        for (int32_t j = 1; j < e->lsn_count[s]; ++j) {
+            const int32_t p = e->lsn_tab[(size_t)s * EWK_LISTENERS_MAX + j].profile;
+            if (p >= n)
+                return fail(EWK_EINVAL, "listener " + std::to_string(j) + " of stream " + std::to_string(s) +
+                                            " points at profile " + std::to_string(p) + " of a table of " +
+                                            std::to_string(n) + ": set its listeners first (ewk_stream_listeners_set)");
+        }
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipStreamSynchronize(e->stream));    // the pushes so far keep their timings
     HIP_TRY(hipStreamSynchronize(e->sstream));
@@ -662,6 +698,183 @@ int ewk_stream_profiles(ewk_engine* e, const int32_t* streams, int32_t n, int32_
     return EWK_OK;
 }
 
+// ---------------------------------------------------------------- stream listeners
+constexpr size_t kLsnRowInts = 2 * EWK_LISTENERS_MAX;   // a stream's table rows as ints
+static_assert(sizeof(ewk_listener) == 8 && sizeof(LsnState) == 40, "listener table layout");
+
+// The per-stream listener arrays, at the first call that gives a stream more than one listener:
+// every stream starts with one listener and zeroed states.  Also the per-stream profile index
+// when no table ever allocated it (all -1): the listener kernels read listener 0's index there.
+static int ensure_listeners(ewk_engine* e, hipStream_t s) {
+    if (e->listeners_on()) return EWK_OK;
+    const size_t n = (size_t)e->n_streams;
+    HIP_TRY(e->d_lsn_count.reserve(n));
+    HIP_TRY(e->d_lsn_tab.reserve(n * EWK_LISTENERS_MAX));
+    HIP_TRY(e->d_lsn_st.reserve(n * kLsnStates));
+    HIP_TRY(e->d_lsn_stage.reserve(n * (kLsnRowInts + 1)));
+    if (!e->h_lsn_stage)
+        HIP_TRY(hipHostMalloc((void**)&e->h_lsn_stage, n * (kLsnRowInts + 1) * sizeof(int32_t), hipHostMallocDefault));
+    if (!e->h_lsn_free) HIP_TRY(hipEventCreateWithFlags(&e->h_lsn_free, hipEventDisableTiming));
+    std::fill(e->h_lsn_stage, e->h_lsn_stage + n, 1);
+    HIP_TRY(hipMemcpyAsync(e->d_lsn_count.p, e->h_lsn_stage, n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(e->h_lsn_free, s));
+    HIP_TRY(hipMemsetAsync(e->d_lsn_tab.p, 0, n * EWK_LISTENERS_MAX * sizeof(ewk_listener), s));
+    HIP_TRY(hipMemsetAsync(e->d_lsn_st.p, 0, n * kLsnStates * sizeof(LsnState), s));
+    if (!e->d_stream_profile.p) {
+        HIP_TRY(e->d_stream_profile.reserve(n));
+        HIP_TRY(hipMemsetAsync(e->d_stream_profile.p, 0xff, n * sizeof(int32_t), s));
+        e->stream_profile.assign(n, -1);
+    }
+    e->lsn_tab.assign(n * EWK_LISTENERS_MAX, ewk_listener{-1, 0});
+    e->lsn_count.assign(n, 1);
+    return EWK_OK;
+}
+
+// with the stream bank on: the per-stream word array exists (ewk_stream_bank_assign's rule)
+static int ensure_stream_words(ewk_engine* e, hipStream_t s) {
+    if (e->sbank_words) return EWK_OK;
+    HIP_TRY(e->sb_word.reserve((size_t)e->n_streams));
+    HIP_TRY(hipMemsetAsync(e->sb_word.p, 0, (size_t)e->n_streams * sizeof(int32_t), s));
+    e->sbank_words = true;
+    return EWK_OK;
+}
+
+int ewk_stream_listeners_set(ewk_engine* e, const int32_t* streams, int32_t n, const int32_t* count,
+                             const ewk_listener* listeners, int32_t stride) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (e->n_streams <= 0) return fail(EWK_EINVAL, "engine has no streams");
+    int rc = check_stream_list(e, streams, n);
+    if (rc) return rc;
+    if (!count) return fail(EWK_EINVAL, "count is NULL");
+    if (!listeners) return fail(EWK_EINVAL, "listeners is NULL");
+    const int32_t n_prof = (int32_t)e->profiles.size();
+    const int32_t n_words = e->sbank_on ? (int32_t)e->bank_first.size() - 1 : 0;
+    bool multi = false;
+    for (int32_t i = 0; i < n; ++i) {
+        if (count[i] < 1 || count[i] > EWK_LISTENERS_MAX)
+            return fail(EWK_EINVAL, "stream " + std::to_string(streams[i]) + ": a stream has 1.." +
+                                        std::to_string(EWK_LISTENERS_MAX) + " listeners, got count " +
+                                        std::to_string(count[i]));
+        if (stride < count[i])
+            return fail(EWK_EINVAL, "stride " + std::to_string(stride) + " is below the count " + std::to_string(count[i]) +
+                                        " of stream " + std::to_string(streams[i]));
+        multi = multi || count[i] > 1;
+    }
+    for (int32_t i = 0; i < n; ++i)
+        for (int32_t j = 0; j < count[i]; ++j) {
+            const ewk_listener& l = listeners[(size_t)i * stride + j];
+            if (l.profile < -1 || l.profile >= n_prof)
+                return fail(EWK_EINVAL, listener_of(streams[i], j) + ": profile " + std::to_string(l.profile) +
+                                            " is outside [-1, " + std::to_string(n_prof) + ")" +
+                                            (n_prof ? "" : " (no profile table is set)"));
+            if (e->sbank_on) {
+                if (l.word < 0 || l.word >= n_words) return fail_listener_word(streams[i], j, l.word, n_words);
+            } else if (l.word != 0) {
+                return fail(EWK_EINVAL, listener_of(streams[i], j) + ": word " + std::to_string(l.word) +
+                                            " while the stream bank is off (the word must be 0)");
+            }
+        }
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    HIP_TRY(join_scoring(e, s));   // (overlap mode: a scoring pass in flight still reads the words)
+    if (e->sbank_on) {
+        rc = ensure_stream_words(e, s);
+        if (rc) return rc;
+    }
+    const int32_t *d_list = nullptr, *d_vals = nullptr;
+    if (!e->listeners_on() && !multi) {   // one listener each and no table to keep: the two assign calls
+        std::vector<int32_t> v((size_t)n);
+        if (n_prof) {
+            for (int32_t i = 0; i < n; ++i) v[i] = listeners[(size_t)i * stride].profile;
+            rc = stage_stream_list(e, streams, v.data(), n, s, &d_list, &d_vals);
+            if (rc) return rc;
+            HIP_TRY(launch_scatter_i32(e->d_stream_profile.p, d_list, d_vals, n, s));
+            for (int32_t i = 0; i < n; ++i) e->stream_profile[streams[i]] = v[i];
+        }
+        if (e->sbank_on) {
+            for (int32_t i = 0; i < n; ++i) v[i] = listeners[(size_t)i * stride].word;
+            rc = stage_stream_list(e, streams, v.data(), n, s, &d_list, &d_vals);
+            if (rc) return rc;
+            HIP_TRY(launch_scatter_i32(e->sb_word.p, d_list, d_vals, n, s));
+            if (e->stream_word.empty()) e->stream_word.assign((size_t)e->n_streams, 0);
+            for (int32_t i = 0; i < n; ++i) e->stream_word[streams[i]] = v[i];
+        }
+        return EWK_OK;
+    }
+    rc = ensure_listeners(e, s);
+    if (rc) return rc;
+    rc = stage_stream_list(e, streams, nullptr, n, s, &d_list, nullptr);
+    if (rc) return rc;
+    // rows (EWK_LISTENERS_MAX per listed stream, whatever the caller's stride), then the counts
+    HIP_TRY(hipEventSynchronize(e->h_lsn_free));   // the previous call's rows have left the staging
+    ewk_listener* h_rows = reinterpret_cast<ewk_listener*>(e->h_lsn_stage);
+    int32_t* h_counts = e->h_lsn_stage + (size_t)n * kLsnRowInts;
+    for (int32_t i = 0; i < n; ++i) {
+        for (int32_t j = 0; j < EWK_LISTENERS_MAX; ++j)
+            h_rows[(size_t)i * EWK_LISTENERS_MAX + j] = j < count[i] ? listeners[(size_t)i * stride + j] : ewk_listener{-1, 0};
+        h_counts[i] = count[i];
+    }
+    HIP_TRY(hipMemcpyAsync(e->d_lsn_stage.p, e->h_lsn_stage, (size_t)n * (kLsnRowInts + 1) * sizeof(int32_t),
+                           hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(e->h_lsn_free, s));
+    ListenerSetArgs a;
+    memset(&a, 0, sizeof(a));
+    a.ids = d_list;
+    a.rows = reinterpret_cast<const ewk_listener*>(e->d_lsn_stage.p);
+    a.counts = e->d_lsn_stage.p + (size_t)n * kLsnRowInts;
+    a.n = n;
+    a.lsn_count = e->d_lsn_count.p;
+    a.lsn_tab = e->d_lsn_tab.p;
+    a.lsn_st = e->d_lsn_st.p;
+    a.st = e->d_st;
+    a.stream_profile = e->d_stream_profile.p;
+    a.stream_word = e->sbank_on ? e->sb_word.p : nullptr;
+    a.tick_seconds = e->cfg.tick_seconds;
+    HIP_TRY(launch_listeners_set(a, s));
+    if (e->sbank_on && e->stream_word.empty()) e->stream_word.assign((size_t)e->n_streams, 0);
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t st = streams[i];
+        e->lsn_multi += (count[i] > 1) - (e->lsn_count[st] > 1);
+        e->lsn_count[st] = count[i];
+        std::copy(h_rows + (size_t)i * EWK_LISTENERS_MAX, h_rows + (size_t)(i + 1) * EWK_LISTENERS_MAX,
+                  e->lsn_tab.begin() + (size_t)st * EWK_LISTENERS_MAX);
+        e->stream_profile[st] = listeners[(size_t)i * stride].profile;
+        if (e->sbank_on) e->stream_word[st] = listeners[(size_t)i * stride].word;
+    }
+    return EWK_OK;
+}
+
+int ewk_stream_listeners(ewk_engine* e, int32_t stream, ewk_listener* out, int32_t cap, int32_t* n_out) {
+    if (!e || !n_out) return fail(EWK_EINVAL, "NULL argument");
+    if (stream < 0 || stream >= e->n_streams) return fail(EWK_EINVAL, "stream index out of range");
+    const int32_t c = e->listeners_on() ? e->lsn_count[stream] : 1;
+    *n_out = c;
+    for (int32_t j = 0; out && j < std::min(c, cap); ++j)
+        out[j] = j ? e->lsn_tab[(size_t)stream * EWK_LISTENERS_MAX + j]
+                   : ewk_listener{e->stream_profile.empty() ? -1 : e->stream_profile[stream],
+                                  e->stream_word.empty() ? 0 : e->stream_word[stream]};
+    return EWK_OK;
+}
+
+int ewk_get_listener_state(ewk_engine* e, int32_t stream, int32_t listener, ewk_stream_state* out) {
+    int rc = ewk_get_stream_state(e, stream, out);
+    if (rc || listener == 0) return rc;
+    const int32_t c = e->listeners_on() ? e->lsn_count[stream] : 1;
+    if (listener < 0 || listener >= c)
+        return fail(EWK_EINVAL, "stream " + std::to_string(stream) + " has " + std::to_string(c) + " listener(s), asked for " +
+                                    std::to_string(listener));
+    LsnState ls;
+    HIP_TRY(hipMemcpyAsync(&ls, e->d_lsn_st.p + (size_t)stream * kLsnStates + listener - 1, sizeof(ls),
+                           hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    out->silence_start_time = ls.silence_start;
+    out->sound_start_time = ls.sound_start;
+    out->sound_end_time = ls.sound_end;
+    out->start_time = ls.start_time;
+    out->state = ls.state;
+    return EWK_OK;
+}
+
 // Event banks are drained in two steps so a failing poll consumes nothing:
 // peek_bank waits for the pushes into bank b (copy stream only, no wait on later
 // work) and fetches its counters with the first kPollChunk events; take_bank copies
@@ -735,9 +948,11 @@ static int overflow(ewk_engine* e, const BankPeek* pk, const int* banks, int nb)
                                 " events of the overflowed bank(s) dropped; the queue was re-armed");
 }
 
-static void sort_events(ewk_event* out, int32_t n) {   // deterministic order: (tick, stream)
+static void sort_events(ewk_event* out, int32_t n) {   // deterministic order: (tick, stream, listener)
     std::sort(out, out + n, [](const ewk_event& x, const ewk_event& y) {
-        return x.tick != y.tick ? x.tick < y.tick : x.stream < y.stream;
+        if (x.tick != y.tick) return x.tick < y.tick;
+        if (x.stream != y.stream) return x.stream < y.stream;
+        return EWK_EV_LISTENER(x.flags) < EWK_EV_LISTENER(y.flags);
     });
 }
 
@@ -798,7 +1013,7 @@ int ewk_reenter(ewk_engine* e, int32_t stream, double reentry_timeout) {
     e->cfg.reentry_timeout = reentry_timeout;   // read by every later gate launch
     const int32_t first = stream < 0 ? 0 : stream;
     const int32_t n = stream < 0 ? e->n_streams : 1;
-    HIP_TRY(launch_reenter(e->d_st, first, n, e->cfg.tick_seconds, e->stream));
+    HIP_TRY(launch_reenter(e->d_st, first, n, e->cfg.tick_seconds, e->d_lsn_count.p, e->d_lsn_st.p, e->stream));
     return EWK_OK;
 }
 

@@ -31,6 +31,19 @@ struct GateStream {
     int32_t spos;            // write position in the sample ring (== pointer when it is the full ring)
 };
 
+// Stream listeners (ewk_stream_listeners_set): the _detect_word locals of listener j >= 1 of a
+// stream (listener 0's are GateStream's); everything else of GateStream is shared.  40 bytes,
+// lsn_st[s * kLsnStates + j - 1].
+struct LsnState {
+    double silence_start;
+    double sound_start;
+    double sound_end;
+    double start_time;
+    int32_t state;
+    int32_t reentries;
+};
+constexpr int kLsnStates = EWK_LISTENERS_MAX - 1;
+
 // numpy's pairwise summation order (np.add.reduce on a contiguous float64 array,
 // numpy/_core/src/umath/loops_utils.h.src pairwise_sum) for ONE chunk of n <= 8192
 // elements, flattened on the host: leaves of <= 128 elements (8-accumulator loop),
@@ -98,6 +111,14 @@ struct GateArgs {
     // without a table: launch_gate then picks the instantiations without the profile code.
     const ewk_detector_profile* profiles;
     const int32_t* stream_profile;   // [n_streams of the engine], by stream (not by row)
+    // Stream listeners: stream s has lsn_count[s] listeners, listener j >= 1 gated with profile
+    // lsn_tab[s * EWK_LISTENERS_MAX + j].profile (-1: the timings above) from state
+    // lsn_st[s * kLsnStates + j - 1], on lane j.  All nullptr while no stream has more than one
+    // listener: launch_gate then picks the instantiations without the listener code.  With them
+    // stream_profile is set (listener 0's index), profiles only when a table exists.
+    const int32_t* lsn_count;
+    const ewk_listener* lsn_tab;
+    LsnState* lsn_st;
 };
 
 // grid_cap > 0: at most that many workgroups (ewk_create's EWK_GATE_GRID_MAX), below the
@@ -118,11 +139,32 @@ struct ResetListArgs {
     float* hist;            // nullptr or [n_streams][H]
     int32_t H;
     uint8_t* fresh;          // nullptr or [n_streams]
+    LsnState* lsn_st;        // nullptr or [n_streams][kLsnStates]: zeroed (the listener table stays)
 };
 hipError_t launch_reset_list(const ResetListArgs& a, hipStream_t s);
 // dst[ids[i]] = vals[i], i < n (ewk_stream_bank_assign)
 hipError_t launch_scatter_i32(int32_t* dst, const int32_t* ids, const int32_t* vals, int32_t n, hipStream_t s);
-hipError_t launch_reenter(GateStream* st, int32_t first, int32_t n, double tick_seconds, hipStream_t s);
+// lsn_count / lsn_st (both nullptr without listeners): every listener of the stream re-enters
+hipError_t launch_reenter(GateStream* st, int32_t first, int32_t n, double tick_seconds, const int32_t* lsn_count,
+                          LsnState* lsn_st, hipStream_t s);
+// ewk_stream_listeners_set: stream ids[i] gets counts[i] listeners rows[i * EWK_LISTENERS_MAX + j];
+// listener 0's entry also goes to stream_profile / stream_word (where not nullptr), a listener at
+// or past the stream's old count starts as k_reenter starts listener 0, a dropped one is zeroed.
+struct ListenerSetArgs {
+    const int32_t* ids;
+    const int32_t* counts;
+    const ewk_listener* rows;
+    int32_t n;
+    int32_t pad0;
+    int32_t* lsn_count;
+    ewk_listener* lsn_tab;
+    LsnState* lsn_st;
+    const GateStream* st;
+    int32_t* stream_profile;
+    int32_t* stream_word;
+    double tick_seconds;
+};
+hipError_t launch_listeners_set(const ListenerSetArgs& a, hipStream_t s);
 // Zero a ring with agent-scope (sc1) stores: the lines go to memory and are dropped from the
 // writing XCD's L2, so no cached copy of the initial zeros outlives the gate's first writes.
 hipError_t launch_ring_zero(void* p, size_t bytes, hipStream_t s);

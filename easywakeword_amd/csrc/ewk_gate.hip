@@ -475,13 +475,106 @@ __device__ __forceinline__ double reg_percentile25(const double (&so)[RB], int n
     return r;
 }
 
+// Listener j >= 1 on its lane (LSN kernels).  The kernels without listeners use 104-124 of the 128
+// VGPRs that 4 waves per SIMD allow, and ten more per lane for a whole LsnState spilled in every
+// family; so a lane keeps in two registers what every tick reads -- state and re-entry count
+// (packed), profile index -- with whether it has a re-entry timeout, and its four times in the
+// wave's LDS (the lane's own words at stride 16, 512 B per wave; the address is formed from the
+// lane index where it is used), read and written on a transition only.
+typedef double __attribute__((address_space(3))) LdsDouble;
+typedef LdsDouble* LdsTimes;
+struct LsnLane {
+    LdsTimes base;        // the wave's LDS words (wave-uniform)
+    int32_t lane;
+    int32_t sr;           // reentries << 2 | state
+    int32_t pi;           // profile index (-1: the launch's timings)
+    bool timeout;         // the listener's re-entry timeout is positive
+    __device__ __forceinline__ int state() const { return sr & 3; }
+    __device__ __forceinline__ void set_state(int v) { sr = (sr & ~3) | v; }
+    __device__ __forceinline__ LdsTimes t() const { return base + (lane_here(lane) & 15); }
+    __device__ __forceinline__ LdsDouble& silence_start() { return t()[0]; }
+    __device__ __forceinline__ LdsDouble& sound_start() { return t()[16]; }
+    __device__ __forceinline__ LdsDouble& sound_end() { return t()[32]; }
+    __device__ __forceinline__ LdsDouble& start_time() { return t()[48]; }
+};
+
+// One _detect_word step of listener j >= 1: the FSM and the cut of k_gate_ticks' listener 0,
+// operation for operation, on the lane's own state.  The six timings are read from the
+// listener's profile where they are compared -- a state transition or the cut -- as per-lane
+// loads, rare and divergent; none is live across a tick.
+__device__ __forceinline__ void lsn_step(LsnLane& ls, const GateArgs& g, bool silent, double now, int s, int j,
+                                         int64_t tick, int spos, int R, int Rs) {
+    const ewk_detector_profile* pf = ls.pi >= 0 ? g.profiles + ls.pi : nullptr;
+#define EWK_LSN_TIMING(field) (pf ? pf->field : g.field)
+    switch (ls.state()) {
+    case kWaiting:
+        if (silent) { ls.set_state(kInSilence); ls.silence_start() = now; }
+        break;
+    case kInSilence:
+        if (!silent) {
+            if (now - ls.silence_start() >= EWK_LSN_TIMING(pre_speech_silence)) { ls.set_state(kInSound); ls.sound_start() = now; }
+            else ls.set_state(kWaiting);
+        }
+        break;
+    case kInSound: {
+        const double d = now - ls.sound_start();
+        if (!silent) {
+            if (d > EWK_LSN_TIMING(speech_duration_max)) ls.set_state(kWaiting);
+        } else {
+            if (EWK_LSN_TIMING(speech_duration_min) <= d && d <= EWK_LSN_TIMING(speech_duration_max)) {
+                ls.set_state(kAfterSound);
+                ls.sound_end() = now;
+            } else ls.set_state(kWaiting);
+        }
+        break;
+    }
+    case kAfterSound:
+        if (silent) {
+            const double sound_end = ls.sound_end();
+            if (now - sound_end >= EWK_LSN_TIMING(post_speech_silence)) {
+                const double xs = ls.sound_start() - now - EWK_LSN_TIMING(padding);
+                const double xe = sound_end - now + EWK_LSN_TIMING(padding);
+                int64_t nreq = (int64_t)(fabs(xs) * (double)g.sample_rate);
+                if (nreq > R) nreq = R;
+                const int64_t e = (int64_t)(fabs(xe) * (double)g.sample_rate);
+                int64_t stop = nreq - e;   // python a[:len-e]
+                if (stop < 0) { stop += nreq; if (stop < 0) stop = 0; }
+                if (stop > nreq) stop = nreq;
+                int64_t start = (int64_t)spos - nreq;
+                if (start < 0) start += Rs;
+                ewk_event ev;
+                ev.stream = s;
+                ev.length = (int32_t)stop;
+                ev.tick = tick;
+                ev.ring_start = start;
+                ev.time = now;
+                ev.score = __builtin_nan("");
+                ev.match = 0;
+                ev.flags = (((double)stop / (double)g.sample_rate > EWK_LSN_TIMING(max_segment_seconds)) ? EWK_EV_SKIPPED : 0) |
+                           (j << EWK_EV_LISTENER_SHIFT);
+                // one slot per cutting lane (several listeners may cut at one tick; the poll sorts)
+                const uint32_t slot = (uint32_t)atomicAdd(g.ev_count, 1) - (uint32_t)g.ev_base0;
+                if (slot < (uint32_t)g.ev_cap) g.events[slot] = ev;
+                else atomicAdd(g.ev_dropped, 1);
+                ls.set_state(kWaiting);
+            }
+        } else ls.set_state(kWaiting);
+        break;
+    }
+#undef EWK_LSN_TIMING
+}
+constexpr size_t kLsnWaveLds = 4 * EWK_LISTENERS_MAX * sizeof(double);   // per wave, behind the two LDS trees
+
 // RB > 0: the stream's block RMS array and its sorted copy live in registers for the
 // whole launch (RB slots per lane, n_blocks <= 64 * RB): loaded once, updated with
 // wave shuffles, stored once -- no dependent global round trips per tick.  RB = 0:
 // both stay in global memory (any n_blocks).
 // PROF (detector profiles): the stream's seven gate timings come from its profile; without it
 // they are the launch's (GateArgs) and the kernel holds no profile code.
-template <int RB, int DMA, bool PROF = false>
+// LSN (stream listeners, with PROF): lane j, 1 <= j < the stream's listener count, carries
+// listener j's _detect_word state in its own registers for the whole launch and steps it after
+// listener 0 at every tick, from the tick's wave-uniform is_silent and clock (lsn_step).
+template <int RB, int DMA, bool PROF = false, bool LSN = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGateWavesPerEU, 8))) void k_gate_ticks(GateArgs g) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -601,6 +694,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGateWavesP
         }
     }
 #define EWK_GATE_TIMING(field) ((PROF && pf) ? pf->field : g.field)
+    // LSN: the count and the lane's profile index once per stream of the loop, then the lane's
+    // 40-byte record (LsnLane: its times go to the lane's LDS words)
+    bool lsn_on = false;
+    LsnLane ls = {};
+    if constexpr (LSN) {
+        const int cnt = min(__builtin_amdgcn_readfirstlane(g.lsn_count[s]), (int)EWK_LISTENERS_MAX);
+        lsn_on = lane >= 1 && lane < cnt;
+        ls.base = (LdsTimes)reinterpret_cast<double*>(smem + 4 * per_wave + 2 * sizeof(PwTree) + wave * kLsnWaveLds);
+        ls.lane = lane;
+        ls.pi = -1;
+        if (lsn_on) {
+            ls.pi = g.lsn_tab[(int64_t)s * EWK_LISTENERS_MAX + lane].profile;
+            const LsnState in = g.lsn_st[(int64_t)s * kLsnStates + lane - 1];
+            ls.silence_start() = in.silence_start;
+            ls.sound_start() = in.sound_start;
+            ls.sound_end() = in.sound_end;
+            ls.start_time() = in.start_time;
+            ls.sr = (in.reentries << 2) | (in.state & 3);
+            ls.timeout = (ls.pi >= 0 ? g.profiles[ls.pi].reentry_timeout : g.reentry_timeout) > 0.0;
+        }
+    }
     const int64_t tick0 = g.own_clock ? st.tick : g.tick0;   // the stream's own clock, or the engine's (equal in lockstep)
     double* grms = g.block_rms + (int64_t)s * nb;
     double* sorted2 = g.sorted_rms + (int64_t)s * 2 * nb;
@@ -629,6 +743,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGateWavesP
             st.start_time = t_prev;
             if (st.last_silent) { st.state = kInSilence; st.silence_start = t_prev; }
             st.reentries += 1;
+        }
+        if constexpr (LSN) {   // the same test per listener, on its own start_time and timeout
+            if (lsn_on && ls.timeout && st.started &&
+                t_prev - ls.start_time() > (ls.pi >= 0 ? g.profiles[ls.pi].reentry_timeout : g.reentry_timeout)) {
+                ls.set_state(kWaiting);
+                ls.start_time() = t_prev;
+                if (st.last_silent) { ls.set_state(kInSilence); ls.silence_start() = t_prev; }
+                ls.sr += 4;   // (reentries += 1)
+            }
         }
         // ---- a1: ingest `fs` samples at the write pointer (and stage them in LDS)
         const int p0 = st.pointer;
@@ -864,6 +987,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGateWavesP
                 st.state = kWaiting;
                 st.start_time = now;
                 if (silent) { st.state = kInSilence; st.silence_start = now; }
+                if constexpr (LSN) {   // every listener enters at the tick the ring fills
+                    if (lsn_on) {
+                        ls.set_state(kWaiting);
+                        ls.start_time() = now;
+                        if (silent) { ls.set_state(kInSilence); ls.silence_start() = now; }
+                    }
+                }
             }
             continue;
         }
@@ -924,6 +1054,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGateWavesP
                 break;
             }
         }
+        if constexpr (LSN) {
+            if (lsn_on) lsn_step(ls, g, silent, now, s, lane, tick, st.spos, R, Rs);
+        }
     }
     if (RB > 0 && (st.filled || g.compact)) {   // only the elements this launch changed (one block RMS per tick)
 #pragma unroll
@@ -934,6 +1067,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGateWavesP
         }
     }
     if (lane == 0) g.st[s] = st;
+    if constexpr (LSN) {
+        if (lsn_on) {
+            LsnState out;
+            out.silence_start = ls.silence_start();
+            out.sound_start = ls.sound_start();
+            out.sound_end = ls.sound_end();
+            out.start_time = ls.start_time();
+            out.state = ls.state();
+            out.reentries = ls.sr >> 2;
+            g.lsn_st[(int64_t)s * kLsnStates + lane - 1] = out;
+        }
+    }
     r += wstride;
     if (r >= g.n_streams) break;
     s = ids ? __builtin_amdgcn_readfirstlane(ids[r]) : r;
@@ -946,7 +1091,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kGateWavesP
 // _detect_word entry (wakeword.py:1048-1057) for streams whose detection runs: state from
 // the current is_silent(), start_time = now.  Streams still filling their ring are left
 // alone (their entry happens in k_gate_ticks when the ring first fills).
-__global__ void k_reenter(GateStream* st, int32_t first, int32_t n, double tick_seconds) {
+__global__ void k_reenter(GateStream* st, int32_t first, int32_t n, double tick_seconds, const int32_t* lsn_count,
+                          LsnState* lsn_st) {
     const int i = first + (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (i >= first + n) return;
     GateStream s = st[i];
@@ -956,6 +1102,55 @@ __global__ void k_reenter(GateStream* st, int32_t first, int32_t n, double tick_
     if (s.last_silent) s.silence_start = now;
     s.start_time = now;
     st[i] = s;
+    if (!lsn_count) return;
+    const int cnt = min(lsn_count[i], (int)EWK_LISTENERS_MAX);
+    for (int j = 1; j < cnt; ++j) {   // every listener of the stream: the same entry
+        LsnState* l = lsn_st + (int64_t)i * kLsnStates + j - 1;
+        l->state = s.state;
+        if (s.last_silent) l->silence_start = now;
+        l->start_time = now;
+    }
+}
+
+// ewk_stream_listeners_set: thread (i, j) handles listener j of stream ids[i] (16 threads per
+// stream, 16 streams per workgroup).  A listener at or past the stream's old count is new and
+// starts as k_reenter starts listener 0 (a stream still filling its ring: zeros, it enters when
+// the ring fills); one at or past the new count is dropped and zeroed.
+__global__ __launch_bounds__(256) void k_listeners_set(const ListenerSetArgs a) {
+    const int i = (int)(blockIdx.x * 16 + (threadIdx.x >> 4)), j = (int)(threadIdx.x & 15);
+    const bool in = i < a.n;
+    const int64_t sid = in ? a.ids[i] : 0;
+    const int newc = in ? a.counts[i] : 0;
+    const int oldc = in ? a.lsn_count[sid] : 0;
+    __syncthreads();   // every thread of the stream has read the old count
+    if (!in) return;
+    const ewk_listener row = j < newc ? a.rows[(int64_t)i * EWK_LISTENERS_MAX + j] : ewk_listener{-1, 0};
+    a.lsn_tab[sid * EWK_LISTENERS_MAX + j] = row;
+    if (j == 0) {
+        a.lsn_count[sid] = newc;
+        if (a.stream_profile) a.stream_profile[sid] = row.profile;
+        if (a.stream_word) a.stream_word[sid] = row.word;
+        return;
+    }
+    if (j < newc && j < oldc) return;   // an existing listener keeps its state
+    LsnState z = {};
+    if (j < newc) {
+        const GateStream g = a.st[sid];
+        if (g.started) {
+            const double now = (double)g.tick * a.tick_seconds;
+            z.state = g.last_silent ? kInSilence : kWaiting;
+            if (g.last_silent) z.silence_start = now;
+            z.start_time = now;
+        }
+    }
+    a.lsn_st[sid * kLsnStates + j - 1] = z;
+}
+
+hipError_t launch_listeners_set(const ListenerSetArgs& a, hipStream_t s) {
+    if (a.n <= 0) return hipSuccess;
+    if (!a.ids || !a.counts || !a.rows || !a.lsn_count || !a.lsn_tab || !a.lsn_st || !a.st) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_listeners_set, dim3((a.n + 15) / 16), dim3(256), 0, s, a);
+    return hipGetLastError();
 }
 
 // Ring initialisation (ewk_reset_streams).  Round 6's recording build caught the ring scorer
@@ -1001,6 +1196,7 @@ __global__ __launch_bounds__(256) void k_reset_list(const ResetListArgs a, const
     for (int k = threadIdx.x; k < a.n_blocks; k += blockDim.x) a.block_rms[sid * a.n_blocks + k] = 0.0;
     if (a.hist)
         for (int k = threadIdx.x; k < a.H; k += blockDim.x) a.hist[sid * a.H + k] = 0.0f;
+    if (a.lsn_st && threadIdx.x < kLsnStates) a.lsn_st[sid * kLsnStates + threadIdx.x] = LsnState{};
     if (threadIdx.x == 0) {
         GateStream z = {};   // (ewk_reset_streams' initial state)
         z.threshold = a.init_threshold;
@@ -1030,9 +1226,11 @@ hipError_t launch_scatter_i32(int32_t* dst, const int32_t* ids, const int32_t* v
     return hipGetLastError();
 }
 
-hipError_t launch_reenter(GateStream* st, int32_t first, int32_t n, double tick_seconds, hipStream_t s) {
+hipError_t launch_reenter(GateStream* st, int32_t first, int32_t n, double tick_seconds, const int32_t* lsn_count,
+                          LsnState* lsn_st, hipStream_t s) {
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_reenter, dim3((n + 255) / 256), dim3(256), 0, s, st, first, n, tick_seconds);
+    if ((lsn_count == nullptr) != (lsn_st == nullptr)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_reenter, dim3((n + 255) / 256), dim3(256), 0, s, st, first, n, tick_seconds, lsn_count, lsn_st);
     return hipGetLastError();
 }
 
@@ -1047,7 +1245,9 @@ hipError_t launch_gate(const GateArgs& g, hipStream_t s, int grid_cap) {
     if (g.n_streams <= 0 || g.n_ticks <= 0) return hipSuccess;
     // one wave per stream (the hardware refills freed slots), up to kGateGridMax workgroups
     const int grid = std::min((g.n_streams + 3) / 4, grid_cap > 0 ? std::min(grid_cap, kGateGridMax) : kGateGridMax);
-    if ((g.profiles == nullptr) != (g.stream_profile == nullptr)) return hipErrorInvalidValue;
+    const bool lsn = g.lsn_count != nullptr;
+    if (lsn ? (!g.lsn_tab || !g.lsn_st || !g.stream_profile) : (g.profiles == nullptr) != (g.stream_profile == nullptr))
+        return hipErrorInvalidValue;
     // (the int16 vector path stages int16; every other path float)
     const int64_t nl = std::min<int64_t>(g.n_last, g.ring_len);
     const bool dma = g.pcm16 == nullptr && g.stage >= g.block && g.stage >= nl;
@@ -1062,7 +1262,24 @@ hipError_t launch_gate(const GateArgs& g, hipStream_t s, int grid_cap) {
     // the DMA 3 instantiations (and only they) stage int16
     const bool i16stage = vec16 && !dma4 && g.n_blocks <= 64 * kGateRegMax;
     const size_t lds = 4 * gate_wave_lds(g.val_len, g.stage, i16stage ? 2 : 4) +
-                       2 * sizeof(PwTree);   // + the two sub-chunk trees (k_gate_ticks)
+                       2 * sizeof(PwTree) +   // + the two sub-chunk trees (k_gate_ticks)
+                       (lsn ? 4 * kLsnWaveLds : 0);   // + the listener lanes' times
+    if (lsn) {   // the families with the per-stream timings and the listener lanes
+        if (g.n_blocks <= 128) {
+            if (dma4) hipLaunchKernelGGL((k_gate_ticks<2, 2, true, true>), dim3(grid), dim3(256), lds, s, g);
+            else if (vec16) hipLaunchKernelGGL((k_gate_ticks<2, 3, true, true>), dim3(grid), dim3(256), lds, s, g);
+            else if (dma) hipLaunchKernelGGL((k_gate_ticks<2, 1, true, true>), dim3(grid), dim3(256), lds, s, g);
+            else hipLaunchKernelGGL((k_gate_ticks<2, 0, true, true>), dim3(grid), dim3(256), lds, s, g);
+        } else if (g.n_blocks <= 64 * kGateRegMax) {
+            if (dma4) hipLaunchKernelGGL((k_gate_ticks<kGateRegMax, 2, true, true>), dim3(grid), dim3(256), lds, s, g);
+            else if (vec16) hipLaunchKernelGGL((k_gate_ticks<kGateRegMax, 3, true, true>), dim3(grid), dim3(256), lds, s, g);
+            else if (dma) hipLaunchKernelGGL((k_gate_ticks<kGateRegMax, 1, true, true>), dim3(grid), dim3(256), lds, s, g);
+            else hipLaunchKernelGGL((k_gate_ticks<kGateRegMax, 0, true, true>), dim3(grid), dim3(256), lds, s, g);
+        } else {
+            hipLaunchKernelGGL((k_gate_ticks<0, 0, true, true>), dim3(grid), dim3(256), lds, s, g);
+        }
+        return hipGetLastError();
+    }
     if (g.profiles) {   // the same families with the per-stream timings
         if (g.n_blocks <= 128) {
             if (dma4) hipLaunchKernelGGL((k_gate_ticks<2, 2, true>), dim3(grid), dim3(256), lds, s, g);

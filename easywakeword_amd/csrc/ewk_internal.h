@@ -222,6 +222,9 @@ struct BankEvArgs {
     const int32_t* stream_word;   // [n_streams]; nullptr: word 0
     int32_t* ev_list;             // [kEvListHdr + capacity]
     int32_t grid;                 // workgroups (fixed per engine: the waves stride over the events)
+    // stream listeners: an event cut by listener j >= 1 (EWK_EV_LISTENER) is scored against word
+    // lsn_tab[stream * EWK_LISTENERS_MAX + j].word; nullptr: no stream has had listeners
+    const ewk_listener* lsn_tab;
 };
 hipError_t launch_bank_events(const BankArgs& b, const ScoreArgs& a, const BankEvArgs& x, hipStream_t s);
 hipError_t launch_bank_events_rescore(const BankArgs& b, const ScoreArgs& a, const BankEvArgs& x, hipStream_t s);

@@ -631,6 +631,44 @@ class StreamEngine(Engine):
         check(self._lib.ewk_stream_profiles(self._h, _lib.i32ptr(s), s.size, _lib.i32ptr(out)))
         return out
 
+    # -- stream listeners: several (profile, word) pairs on one stream ---------------
+    def set_stream_listeners(self, streams, listeners, stride: Optional[int] = None) -> None:
+        """Stream streams[i] has the listeners listeners[i] from the next push on: a sequence of
+        1.._lib.EWK_LISTENERS_MAX (profile, word) pairs; a bare int is a profile with word 0.  All
+        listeners of a stream share its ring, threshold and clock; each runs its own detector with
+        its profile's timings (-1: the engine's configuration), and its events -- listener index
+        in _lib.event_listener(flags) -- are scored against its word of the stream bank.  Listener
+        0 is the stream's own profile and word (assign_stream_profiles / assign_stream_words).
+        A listener that existed keeps its state, a new one starts as reenter() starts a stream.
+        Stream-ordered, no wait.  ValueError (nothing changes) names the stream, listener and
+        field of a bad count, profile or word.  `stride` (default: the longest list) is the row
+        length of the table handed to the library."""
+        s = self._stream_list(streams)
+        rows = [[(int(l), 0) if np.isscalar(l) else (int(l[0]), int(l[1])) for l in row] for row in listeners]
+        if len(rows) != s.size:
+            raise ValueError(f"{len(rows)} listener lists for {s.size} streams")
+        count = np.array([len(r) for r in rows], np.int32)
+        stride = max(1, int(count.max())) if stride is None else int(stride)
+        tab = (_lib.EwkListener * (max(1, stride) * s.size))()
+        for i, row in enumerate(rows):
+            for j, (p, w) in enumerate(row[:max(0, stride)]):
+                tab[i * stride + j] = _lib.EwkListener(p, w)
+        check(self._lib.ewk_stream_listeners_set(self._h, _lib.i32ptr(s), s.size, _lib.i32ptr(count), tab, stride))
+
+    def stream_listeners(self, stream: int) -> list:
+        """The listeners of `stream` as (profile, word) pairs (host bookkeeping, no wait): one
+        pair, the stream's own profile and word, for a stream never given listeners."""
+        out = (_lib.EwkListener * _lib.EWK_LISTENERS_MAX)()
+        n = C.c_int32(0)
+        check(self._lib.ewk_stream_listeners(self._h, int(stream), out, _lib.EWK_LISTENERS_MAX, C.byref(n)))
+        return [(int(out[j].profile), int(out[j].word)) for j in range(int(n.value))]
+
+    def listener_state(self, stream: int, listener: int) -> dict:
+        """state(stream) with the detector fields (state and the four times) of `listener`."""
+        st = _lib.EwkStreamState()
+        check(self._lib.ewk_get_listener_state(self._h, int(stream), int(listener), C.byref(st)))
+        return {f: getattr(st, f) for f, _ in st._fields_}
+
     # -- stream bank: gated events against many references, per stream ------------
     def set_stream_bank(self, stream_word=None) -> None:
         """From the next push on, every gated event of stream s is scored on the device against

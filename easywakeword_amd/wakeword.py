@@ -647,3 +647,190 @@ class WakeWord:
             self.stop()
         except Exception:
             pass
+
+
+class WakeWordSet:
+    """Several wake words on one microphone: one SoundBuffer on a one-stream engine whose stream
+    has one listener per word (StreamEngine.set_stream_listeners).  What the reference does with
+    several WakeWord objects on one device (examples/multi_stage.py), with one ring, one ingest
+    and one threshold pass per tick: listener i is gated with the timings a WakeWord built from
+    words[i] would use (detector_profile) and its events are scored, on the device, against the
+    recordings of words[i] (word i of the engine's bank) at that entry's threshold.
+
+    words -- a list of dicts of WakeWord's keywords: textword, wavword (a file or several),
+             similarity_threshold, pre_speech_silence, speech_duration_min, speech_duration_max,
+             post_speech_silence, numberofwords, confirm (a level-3 callable as WakeWord's, applied
+             to that entry's matches as WakeWord._handle_events applies it).
+    waitforit() returns the textword of the first matching event (last_index: its entry) and
+    raises TimeoutError like WakeWord; start(callback) / stop() / is_listening() as in WakeWord,
+    except that a detection starts a new _detect_word call for every word, not only its own.
+    """
+
+    _PROFILE_KEYS = ("pre_speech_silence", "speech_duration_min", "speech_duration_max", "post_speech_silence")
+
+    def __init__(self, words, source=None, timeout: int = 30, gpu: int = 0, device=None,
+                 callback: Optional[Callable[[str], None]] = None, buffer_seconds: int = DEFAULT_BUFFER_SECONDS,
+                 verbose: bool = False):
+        words = [dict(w) for w in words]
+        if not 1 <= len(words) <= _lib.EWK_LISTENERS_MAX:
+            raise ValueError(f"a WakeWordSet holds 1..{_lib.EWK_LISTENERS_MAX} words, got {len(words)}")
+        if buffer_seconds <= 0:
+            raise ValueError("buffer_seconds must be positive")
+        self._entries = []
+        for i, w in enumerate(words):
+            if "textword" not in w or "wavword" not in w:
+                raise ValueError(f"words[{i}] needs textword and wavword")
+            wav = w.pop("wavword")
+            wavs = [wav] if isinstance(wav, (str, bytes)) or hasattr(wav, "__fspath__") else list(wav)
+            if not wavs:
+                raise ValueError(f"words[{i}]: wavword must name at least one reference file")
+            text = w.pop("textword").lower().strip()
+            entry = dict(textword=text, wavwords=wavs, threshold=float(w.pop("similarity_threshold", 75.0)),
+                         numberofwords=int(w.pop("numberofwords", 2)), confirm=w.pop("confirm", None),
+                         timings={k: w.pop(k) for k in self._PROFILE_KEYS if k in w})
+            if w:
+                raise TypeError(f"words[{i}]: unknown key(s) {sorted(w)}")
+            self._entries.append(entry)
+        self.textwords = [e["textword"] for e in self._entries]
+        self.timeout = timeout
+        self.callback = callback
+        self.device = device
+        self.buffer_seconds = buffer_seconds
+        self.verbose = verbose
+        self.last_index: Optional[int] = None
+        self._source = source
+        self._gpu = gpu
+        self._sound_buffer: Optional[SoundBuffer] = None
+        self._listening = False
+        self._listen_thread: Optional[threading.Thread] = None
+        self._stop_event = threading.Event()
+
+    def _log(self, message: str, level: int = logging.DEBUG) -> None:
+        if self.verbose:
+            logger.log(level, message)
+
+    def _initialize_audio(self, reentry: bool = False) -> None:
+        """Buffer, bank, profile table and listeners on first use; every call is a new
+        _detect_word entry for every word, in the mode of its caller (WakeWord._initialize_audio)."""
+        timeout = float(self.timeout) if reentry else 0.0
+        if self._sound_buffer is None:
+            src = self._source if self._source is not None else _default_source(self.device)
+            self._sound_buffer = SoundBuffer(self.buffer_seconds, source=src, gpu=self._gpu)
+            eng = self._sound_buffer.engine
+            eng.bank_from_pcm([[_audio.load_wav(f) for f in e["wavwords"]] for e in self._entries],
+                              thresholds=[e["threshold"] for e in self._entries])
+            eng.set_stream_bank()
+            self._profiles = [detector_profile(e["wavwords"], e["textword"], **e["timings"]) for e in self._entries]
+            first = True
+        else:
+            eng, first = self._sound_buffer.engine, False
+        # the words' re-entry timeout is the caller's mode, like the engine's own
+        for p in self._profiles:
+            p.reentry_timeout = timeout
+        if first or eng.detector_profiles()[0].reentry_timeout != timeout:
+            eng.set_detector_profiles(self._profiles)
+        if first:
+            eng.set_stream_listeners([0], [[(i, i) for i in range(len(self._entries))]])
+        eng.reenter(0, timeout)
+
+    def _wait_for_buffer(self) -> None:
+        while not self._sound_buffer.is_buffer_full():
+            if self._stop_event.is_set():
+                return
+            self._sound_buffer.pump()
+
+    def _confirmed(self, entry: dict, ev) -> bool:
+        """WakeWord's level 3 for one entry (its confirm callable and word checks)."""
+        if entry["confirm"] is None:
+            return True
+        eng = self._sound_buffer.engine
+        audio = eng.read_segment(0, int(ev["ring_start"]), int(ev["length"]))
+        try:
+            text = entry["confirm"](normalize_for_transcription(audio, eng))
+        except Exception as e:  # noqa: BLE001 - as WakeWord._transcribe_audio
+            self._log(f"Transcription failed: {e}", logging.ERROR)
+            return False
+        if not text:
+            return False
+        said = text.strip().lower().rstrip(".,!?;:").split()
+        return len(said) == entry["numberofwords"] and all(w in said for w in entry["textword"].split())
+
+    def _handle_events(self, events) -> Optional[str]:
+        for ev in events:   # (tick, stream, listener) order: the first match of the earliest tick
+            if ev["flags"] & _lib.EWK_EV_SKIPPED:
+                continue
+            i = int(_lib.event_listener(int(ev["flags"])))
+            self._log(f"MFCC similarity to '{self.textwords[i]}': {ev['score']:.1f}%")
+            if ev["match"] and self._confirmed(self._entries[i], ev):
+                self.last_index = i
+                return self.textwords[i]
+        return None
+
+    def _detect_word(self) -> Optional[str]:
+        eng = self._sound_buffer.engine
+        start_tick = eng.state(0)["tick"]
+        while not self._stop_event.is_set():
+            if (eng.state(0)["tick"] - start_tick) * 0.1 > self.timeout:
+                raise TimeoutError(f"Wake word detection timed out after {self.timeout} seconds")
+            self._sound_buffer.pump()
+            res = self._handle_events(eng.poll())
+            if res is not None:
+                return res
+        return None
+
+    def waitforit(self) -> str:
+        self._initialize_audio()
+        self._stop_event.clear()
+        self._listening = True
+        try:
+            self._wait_for_buffer()
+            result = self._detect_word()
+            if result is None:
+                raise TimeoutError(f"Wake word detection timed out after {self.timeout} seconds")
+            return result
+        finally:
+            self._listening = False
+
+    def start(self, callback: Optional[Callable[[str], None]] = None) -> None:
+        if callback is not None:
+            self.callback = callback
+        if self.callback is None:
+            raise ValueError("Callback must be set for async operation. Use waitforit() for synchronous operation.")
+        if self._listening:
+            return
+        self._initialize_audio(reentry=True)
+        self._stop_event.clear()
+        self._listening = True
+
+        def listen_loop():
+            try:
+                self._wait_for_buffer()
+                eng = self._sound_buffer.engine
+                while not self._stop_event.is_set():
+                    self._sound_buffer.pump()
+                    res = self._handle_events(eng.poll())
+                    if res and self.callback:
+                        self.callback(res)
+                        eng.reenter(0, float(self.timeout))
+            finally:
+                self._listening = False
+
+        self._listen_thread = threading.Thread(target=listen_loop, daemon=True)
+        self._listen_thread.start()
+
+    def stop(self) -> None:
+        self._stop_event.set()
+        if self._listen_thread and self._listen_thread.is_alive():
+            self._listen_thread.join(timeout=2.0)
+        if self._sound_buffer:
+            self._sound_buffer.stop()
+        self._listening = False
+
+    def is_listening(self) -> bool:
+        return self._listening
+
+    def __del__(self):
+        try:
+            self.stop()
+        except Exception:
+            pass

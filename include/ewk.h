@@ -259,7 +259,7 @@ int ewk_push_many(ewk_engine* e, const float* pcm, int64_t stride, int64_t tick_
 int ewk_push_pcm16(ewk_engine* e, const int16_t* pcm, int64_t stride, int32_t flags);
 int ewk_push_many_pcm16(ewk_engine* e, const int16_t* pcm, int64_t stride, int64_t tick_stride,
                         int32_t n_ticks, int32_t flags);
-/* Drain every queued event (waits for every push so far), sorted by (tick, stream).
+/* Drain every queued event (waits for every push so far), sorted by (tick, stream, listener).
  * If more than `cap` are queued nothing is consumed and EWK_EINVAL is returned (poll
  * again with a larger buffer).  If a bank overflowed (more than max(4096, 4 * n_streams)
  * events between polls) its events are dropped, the queue is re-armed so later pushes
@@ -403,6 +403,63 @@ int ewk_stream_profile_assign(ewk_engine* e, const int32_t* streams, int32_t n, 
 /* The profile of each listed stream (streams NULL: streams 0..n-1); all -1 without a table.
  * Host mirror: no device access, no wait. */
 int ewk_stream_profiles(ewk_engine* e, const int32_t* streams, int32_t n, int32_t* out);
+
+/* ---- level 1 for several words on one microphone: stream listeners ---------------------- */
+/* In the reference a room that listens for several words is several WakeWord objects on one
+ * device (examples/multi_stage.py): one SoundBuffer, and per WakeWord its own _detect_word call,
+ * timings and reference word.  A stream has 1..EWK_LISTENERS_MAX listeners; a listener is a pair
+ * (detector profile, word of the stream bank).  All listeners of a stream share its ring, its block
+ * RMSs and adaptive threshold, is_silent, its clock and its `started` flag -- one ingest and one
+ * threshold pass per tick whatever their number.  Each listener has its own _detect_word state
+ * (state, silence_start, sound_start, sound_end, start_time, re-entries), its own timings and its
+ * own word: it cuts and queues its own events, each scored against its word, and the events that
+ * carry (stream s, listener j) are exactly those of a one-stream engine configured with the
+ * listener's profile and word and fed the same blocks -- every field and the score's bits, flags
+ * apart from the listener bits.  Listeners multiply a stream's event rate; the event queues keep
+ * their capacity (max(4096, 4 * n_streams) events between polls) and their overflow behaviour.
+ *
+ * Listener 0 is what a stream has without this section: the FSM of ewk_get_stream_state, the
+ * profile of ewk_stream_profile_assign, the word of ewk_stream_bank_assign (both calls keep
+ * addressing listener 0).  A stream that was never set has that one listener, and an engine
+ * without a stream of more than one listener runs the gate kernels it ran before.
+ *
+ * ewk_reset_streams / ewk_reset_stream_list return every listener's state to the initial state
+ * and keep the table, as they keep profile and word assignments.  ewk_reenter re-enters every
+ * listener of the stream(s).  ewk_detector_profiles_set refuses to shorten (or clear) a table a
+ * listener still points past, and ewk_stream_bank_enable a bank without a listener's word; both
+ * name the stream and the listener and change nothing.  ewk_poll / ewk_poll_lagged sort by (tick,
+ * stream, listener). */
+#define EWK_LISTENERS_MAX 16
+#define EWK_EV_LISTENER_SHIFT 16          /* bits 16..19 of ewk_event.flags: the listener that cut the event */
+#define EWK_EV_LISTENER(flags) (((flags) >> EWK_EV_LISTENER_SHIFT) & 15)
+typedef struct ewk_listener { int32_t profile; int32_t word; } ewk_listener;   /* profile -1: the engine's configuration */
+
+/* Stream streams[i] has count[i] (1..EWK_LISTENERS_MAX) listeners from the next push on:
+ * listeners[i * stride + j], j < count[i].  Host arrays, `streams` as for ewk_push_streams.
+ * Everything is validated before anything is enqueued or changed: every count in
+ * [1, EWK_LISTENERS_MAX], stride >= the largest count, every profile in [-1, n_profiles) (-1 only,
+ * without a table), every word in [0, n_words) while the stream bank is on and 0 while it is off
+ * -- else EWK_EINVAL naming the stream, the listener and the field.  Stream-ordered behind the
+ * pushes so far and their scoring, no host wait; a lockstep engine stays in lockstep.
+ *   listener 0      its entry is written through to the stream's profile index and word, as the two
+ *                   assign calls would; its FSM state and the stream's clock are untouched.
+ *   j >= 1, old     a listener that existed keeps its FSM state and gets the new numbers.
+ *   j >= 1, new     starts as a new _detect_word call starts: on a started stream as ewk_reenter
+ *                   starts listener 0 (state from the last is_silent, silence_start and start_time =
+ *                   the stream's tick * tick_seconds); on a stream whose ring is still filling it
+ *                   enters at the tick the ring fills, together with listener 0.
+ *   dropped         a listener at or past a smaller count loses its state; re-added later it is new.
+ * The first call that gives a stream more than one listener allocates the per-stream table, states
+ * and count on the device (16 x 8 + 15 x 40 + 4 = 732 bytes per stream) and the host mirror (132
+ * bytes per stream), freed with the engine. */
+int ewk_stream_listeners_set(ewk_engine* e, const int32_t* streams, int32_t n, const int32_t* count,
+                             const ewk_listener* listeners, int32_t stride);
+/* Host mirror, no device access: *n_out listeners of `stream` (1 for a stream never set).  Up to
+ * `cap` of them are written to `out` (may be NULL with cap 0). */
+int ewk_stream_listeners(ewk_engine* e, int32_t stream, ewk_listener* out, int32_t cap, int32_t* n_out);
+/* ewk_get_stream_state with the FSM fields (state and the four times) of listener `listener`
+ * (0: the same as ewk_get_stream_state); EWK_EINVAL for a listener the stream does not have. */
+int ewk_get_listener_state(ewk_engine* e, int32_t stream, int32_t listener, ewk_stream_state* out);
 
 /* ---- either side of the path --------------------------------------- */
 /* Level-3 input: WakeWord._transcribe_audio's normalisation (wakeword.py:1019-1025)
