@@ -47,6 +47,7 @@ EWK_BANK_MAX_TEMPLATES = 65536
 EWK_PROFILE_MAX = 65536
 EWK_LISTENERS_MAX = 16       # listeners (detector profile, word) per stream
 EWK_EV_LISTENER_SHIFT = 16   # bits 16..19 of an event's flags: the listener that cut it
+EWK_CHUNK_MAX_TICKS = 64     # a chunk holds at most this many input blocks (ewk_push_chunks)
 
 # Every symbol include/ewk.h declares (checked by tests/test_capi.py).
 EXPORTS = [
@@ -68,6 +69,7 @@ EXPORTS = [
     "ewk_default_detector_profile", "ewk_detector_profiles_set", "ewk_detector_profiles_info",
     "ewk_detector_profile_get", "ewk_stream_profile_assign", "ewk_stream_profiles",
     "ewk_stream_listeners_set", "ewk_stream_listeners", "ewk_get_listener_state",
+    "ewk_push_chunks", "ewk_push_chunks_pcm16", "ewk_stream_pending", "ewk_chunk_plan",
 ]
 
 
@@ -237,6 +239,11 @@ def load():
             "ewk_stream_listeners_set": (C.c_int, [_P, _i32p, C.c_int32, _i32p, C.POINTER(EwkListener), C.c_int32]),
             "ewk_stream_listeners": (C.c_int, [_P, C.c_int32, C.POINTER(EwkListener), C.c_int32, _i32p]),
             "ewk_get_listener_state": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(EwkStreamState)]),
+            "ewk_push_chunks": (C.c_int, [_P, _i32p, C.c_int32, _P, C.c_int64, _i64p, _i32p, C.c_int32]),
+            "ewk_push_chunks_pcm16": (C.c_int, [_P, _i32p, C.c_int32, _P, C.c_int64, _i64p, _i32p, C.c_int32]),
+            "ewk_stream_pending": (C.c_int, [_P, _i32p, C.c_int32, _i32p]),
+            "ewk_chunk_plan": (C.c_int, [C.c_int32, C.c_int32, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p,
+                                         C.c_int32, _i32p]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)

@@ -79,15 +79,24 @@ class ArraySource:
     """Blocks from an in-memory float32 signal; zeros after the end (a silent mic).
     ``rate``: the signal's sample rate.  At another rate than 16 kHz every read yields the
     tick's samples at that rate (``block * rate / 16000``; ``block`` stays the 16 kHz tick the
-    engine is built with) and the engine resamples them on the device."""
+    engine is built with) and the engine resamples them on the device.
+    ``read_sizes``: an int, or a sequence that is cycled -- every read yields that many input
+    samples instead of a tick's (a network source's packets; the engine re-blocks them on the
+    device, StreamEngine.push_chunks)."""
 
     realtime = False
 
-    def __init__(self, audio, block: int = 1600, loop: bool = False, rate: int = FREQUENCY):
+    def __init__(self, audio, block: int = 1600, loop: bool = False, rate: int = FREQUENCY, read_sizes=None):
         self.audio = np.ascontiguousarray(np.asarray(audio, dtype=np.float32).reshape(-1))
         self.block = int(block)
         self.rate = int(rate)
         self.read_block = input_block(self.block, self.rate)
+        if read_sizes is not None:
+            read_sizes = [int(read_sizes)] if np.isscalar(read_sizes) else [int(n) for n in read_sizes]
+            if not read_sizes or min(read_sizes) < 0 or max(read_sizes) == 0:
+                raise ValueError("read_sizes must hold sample counts >= 0, one of them positive")
+        self.read_sizes = read_sizes
+        self.reads = 0
         self.loop = loop
         self.pos = 0
 
@@ -97,7 +106,8 @@ class ArraySource:
             yield b
 
     def read(self) -> np.ndarray:
-        n = self.read_block
+        n = self.read_block if self.read_sizes is None else self.read_sizes[self.reads % len(self.read_sizes)]
+        self.reads += 1
         a = self.audio
         if self.loop and len(a):
             idx = (self.pos + np.arange(n)) % len(a)
@@ -138,11 +148,15 @@ class MicSource:
     """PortAudio microphone through ``sounddevice`` (only when installed); `device` is a
     PortAudio index -- easywakeword_amd.devices.AudioDeviceManager resolves names and
     the reference's magic words.  ``samplerate``: open the device at its own rate (no
-    conversion inside PortAudio); the engine resamples the blocks on the device."""
+    conversion inside PortAudio); the engine resamples the blocks on the device.
+    ``blocksize``: frames per callback -- None: a tick's (``read_block``), 0: PortAudio chooses, as
+    the reference opens its stream; reads of any other length than a tick are re-blocked on the
+    device (StreamEngine.push_chunks)."""
 
     realtime = True
 
-    def __init__(self, device: Optional[int] = None, block: int = 1600, samplerate: int = FREQUENCY):
+    def __init__(self, device: Optional[int] = None, block: int = 1600, samplerate: int = FREQUENCY,
+                 blocksize: Optional[int] = None):
         import queue
 
         import sounddevice as sd  # noqa: F401  (raises ImportError/OSError when absent)
@@ -151,7 +165,8 @@ class MicSource:
         self.rate = int(samplerate)
         self.read_block = input_block(self.block, self.rate)
         self.q: "queue.Queue[np.ndarray]" = queue.Queue()
-        self.stream = sd.InputStream(samplerate=self.rate, channels=1, blocksize=self.read_block, device=device,
+        self.blocksize = self.read_block if blocksize is None else int(blocksize)
+        self.stream = sd.InputStream(samplerate=self.rate, channels=1, blocksize=self.blocksize, device=device,
                                      callback=lambda indata, frames, t, status: self.q.put(
                                          np.array(indata, dtype=np.float32).reshape(-1).copy()))
 

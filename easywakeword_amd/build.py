@@ -14,9 +14,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["ewk_mfcc.hip", "ewk_bank.hip", "ewk_gate.hip", "ewk_level3.hip", "ewk_gather.hip", "ewk_resample.hip",
-           "ewk_engine.cpp", "ewk_engine_score.cpp", "ewk_engine_stream.cpp", "ewk_engine_resample.cpp",
+           "ewk_chunks.hip", "ewk_engine.cpp", "ewk_engine_score.cpp", "ewk_engine_stream.cpp", "ewk_engine_resample.cpp",
            "ewk_tables.cpp"]
-HEADERS = ["ewk_internal.h", "ewk_engine.h", "ewk_gate.h", "ewk_rescore.h", "ewk_rs_list.h", "ewk_score.h", "ewk_db64.h", "ewk_topdb_shift.h",
+HEADERS = ["ewk_internal.h", "ewk_engine.h", "ewk_gate.h", "ewk_rescore.h", "ewk_rs_list.h", "ewk_score.h", "ewk_db64.h", "ewk_topdb_shift.h", "ewk_chunk_plan.h",
            os.path.join("..", "..", "include", "ewk.h")]
 LIB = os.path.join(HERE, "libewk.so")
 ARCH = os.environ.get("EWK_OFFLOAD_ARCH", "gfx950")

@@ -149,6 +149,8 @@ void ewk_destroy(ewk_engine* e) {
     if (e->h_ids_free) (void)hipEventDestroy(e->h_ids_free);
     if (e->h_lsn_stage) (void)hipHostFree(e->h_lsn_stage);
     if (e->h_lsn_free) (void)hipEventDestroy(e->h_lsn_free);
+    if (e->h_chunk) (void)hipHostFree(e->h_chunk);
+    if (e->h_chunk_free) (void)hipEventDestroy(e->h_chunk_free);
     (void)hipFree(e->d_ring);
     (void)hipFree(e->d_brms);
     (void)hipFree(e->d_sorted);
@@ -381,7 +383,7 @@ int ewk_profile_enable(ewk_engine* e, int32_t on) {
 
 int ewk_profile_read(ewk_engine* e, int32_t kind, double* total_ms, int64_t* launches) {
     if (!e || !total_ms || !launches) return fail(EWK_EINVAL, "NULL argument");
-    if (kind < 0 || kind > 3) return fail(EWK_EINVAL, "kind must be 0, 1, 2 or 3");
+    if (kind < 0 || kind > 4) return fail(EWK_EINVAL, "kind must be 0, 1, 2, 3 or 4");
     HIP_TRY(hipSetDevice(e->device));
     double tot = 0.0;
     for (auto& p : e->ev[kind]) {

@@ -208,6 +208,29 @@ struct ewk_engine {
     hipEvent_t h_lsn_free = nullptr;           // recorded after the last DMA out of h_lsn_stage
     std::vector<int32_t> stream_word;          // host mirror of sb_word (empty: word 0 everywhere)
     bool listeners_on() const { return !lsn_count.empty(); }
+    // Packet ingest (ewk_push_chunks*, ewk_chunks.hip); everything is allocated by the first chunk
+    // push.  chunk_carry: per stream the samples of its unfinished block, in_block elements of the
+    // ring's type ([n_streams][in_block]; regrown when a larger input block is set, which is only
+    // possible while nothing is pending).  chunk_pending: its host mirror, samples held per stream
+    // (every device read of a carry row is bounded by it, so dropping samples needs no device
+    // work); chunk_pending_n: streams holding any.  chunk_asm: the tick rows of one push, grown to
+    // the largest push so far.  h_chunk -> d_chunk: a push's descriptors ([n_streams] ChunkDesc)
+    // followed by its ticking streams in plan order ([n_streams] int32, the gate's index lists).
+    ewk::DevBuf<unsigned char> chunk_carry, chunk_asm, d_chunk;
+    std::vector<int32_t> chunk_pending;        // [n_streams]; empty: no chunk push yet
+    int32_t chunk_pending_n = 0;
+    unsigned char* h_chunk = nullptr;          // pinned
+    hipEvent_t h_chunk_free = nullptr;         // recorded after the last DMA out of h_chunk
+    std::vector<int32_t> chunk_plan_buf;       // a push's plan (ewk_chunk_plan.h), 5 ints per listed stream
+    void drop_pending(int32_t s) {
+        if (chunk_pending.empty() || chunk_pending[s] == 0) return;
+        chunk_pending[s] = 0;
+        chunk_pending_n -= 1;
+    }
+    void drop_all_pending() {
+        std::fill(chunk_pending.begin(), chunk_pending.end(), 0);
+        chunk_pending_n = 0;
+    }
     int32_t gate_grid_cap = 0;     // EWK_GATE_GRID_MAX at ewk_create: workgroups per gate launch (0: the built-in maximum)
     int32_t gate_stage = 0;
     int32_t gate_val_len = 0;       // per-wave LDS doubles of the gate (tree values, sort scratch)
@@ -232,7 +255,7 @@ struct ewk_engine {
 
     // measurement: (start, stop) event pairs per kernel family
     bool prof = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[4];
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[5];
     std::vector<hipEvent_t> ev_pool;
 };
 

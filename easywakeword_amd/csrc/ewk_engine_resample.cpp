@@ -158,6 +158,7 @@ int ewk_set_input_rate(ewk_engine* e, int32_t in_rate) {
         if (!e->rs_on) return EWK_OK;
         HIP_TRY(hipStreamSynchronize(e->stream));
         e->rs_on = false;
+        e->drop_all_pending();   // (pending chunk samples were counted at the old rate)
         return EWK_OK;
     }
     if (e->ring_es == sizeof(int16_t))
@@ -169,6 +170,7 @@ int ewk_set_input_rate(ewk_engine* e, int32_t in_rate) {
                                     std::to_string(e->cfg.sample_rate) + " Hz is not a whole number of samples at " +
                                     std::to_string(in_rate) + " Hz");
     e->rs_on = false;   // (a failure below leaves the engine at its own rate)
+    e->drop_all_pending();   // the unit of a pending chunk count changes with the rate, also on that failure
     int rc = rs_prepare(e, e->rs_in, in_rate, true);   // waits for the pushes so far when the rate changes
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));

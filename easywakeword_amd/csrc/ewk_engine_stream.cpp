@@ -3,6 +3,8 @@
 // ring reads.
 #include "ewk_engine.h"
 
+#include "ewk_chunk_plan.h"
+
 using namespace ewk;
 
 static void zero_event_state(ewk_engine* e) {
@@ -61,6 +63,7 @@ int ewk_reset_streams(ewk_engine* e) {
     e->tick = 0;
     e->desync = false;   // one clock again
     std::vector<int64_t>().swap(e->tick_delta);
+    e->drop_all_pending();   // (the carry rows stay as they are: every read of one is bounded by its pending count)
     return EWK_OK;
 }
 
@@ -386,6 +389,29 @@ static int finish_push(ewk_engine* e, hipStream_t s) {
     return EWK_OK;
 }
 
+static int gate_ticks(ewk_engine* e, const TickSrc& src, int32_t rows, int32_t n_ticks, const int32_t* d_list,
+                      const int32_t* streams, hipStream_t s);
+
+// A tick push to a stream that holds the samples of an unfinished block (ewk_push_chunks) would
+// put its audio out of order.  (Nothing is ever pending on an engine that was never chunk-pushed.)
+static int fail_pending(ewk_engine* e, int32_t s) {
+    return fail(EWK_EINVAL, "stream " + std::to_string(s) + " holds " + std::to_string(e->chunk_pending[s]) +
+                                " pending samples of an unfinished block (ewk_push_chunks): a tick push would put them "
+                                "out of order; finish the block with ewk_push_chunks or reset the stream");
+}
+
+static int check_nothing_pending(ewk_engine* e, const int32_t* streams, int32_t n_list) {
+    if (e->chunk_pending_n == 0) return EWK_OK;
+    if (streams) {
+        for (int32_t i = 0; i < n_list; ++i)
+            if (e->chunk_pending[streams[i]] > 0) return fail_pending(e, streams[i]);
+        return EWK_OK;
+    }
+    for (int32_t s = 0; s < e->n_streams; ++s)
+        if (e->chunk_pending[s] > 0) return fail_pending(e, s);
+    return EWK_OK;
+}
+
 // streams == nullptr: a tick for every stream (row s of pcm is stream s); else rows 0..n_list-1
 // are the ticks of streams[0..n_list) (ewk_push_streams).
 static int push_impl(ewk_engine* e, const void* pcm_any, int64_t stride, int64_t tick_stride, int32_t n_ticks,
@@ -405,6 +431,10 @@ static int push_impl(ewk_engine* e, const void* pcm_any, int64_t stride, int64_t
     const int64_t in_block = e->rs_on ? e->rs_in_block : e->cfg.block;
     if (stride < in_block && rows > 1)
         return fail(EWK_EINVAL, e->rs_on ? "stride must be >= the input block (ewk_input_rate_info)" : "stride must be >= block");
+    {
+        int rc = check_nothing_pending(e, streams, n_list);
+        if (rc) return rc;
+    }
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = e->stream;
     int rc = EWK_OK;
@@ -416,7 +446,16 @@ static int push_impl(ewk_engine* e, const void* pcm_any, int64_t stride, int64_t
     TickSrc src{pcm_any, pcm16, stride, tick_stride};
     if (rc == EWK_OK && !(flags & EWK_PUSH_DEVICE)) rc = stage_host_ticks(e, &src, rows, n_ticks, in_block, s);
     if (rc == EWK_OK && e->rs_on) rc = resample_ticks(e, &src, rows, n_ticks, d_list, s);
+    if (rc == EWK_OK) rc = gate_ticks(e, src, rows, n_ticks, d_list, streams, s);
     if (rc) return rc;
+    return finish_push(e, s);
+}
+
+// The gate launches of a push, each with its scoring pass behind it: n_ticks ticks at src for
+// `rows` streams -- all of them (d_list and streams nullptr), or those of the index list (on the
+// device and on the host).  Updates the tick mirror.
+static int gate_ticks(ewk_engine* e, const TickSrc& src, int32_t rows, int32_t n_ticks, const int32_t* d_list,
+                      const int32_t* streams, hipStream_t s) {
     GateArgs g = gate_args(e);
     g.stride = src.stride;
     g.tick_stride = src.tick_stride;
@@ -440,12 +479,12 @@ static int push_impl(ewk_engine* e, const void* pcm_any, int64_t stride, int64_t
             HIP_TRY(launch_gate(g, s, e->gate_grid_cap));
         }
         if (!streams) e->tick += nt;
-        else for (int32_t i = 0; i < n_list; ++i) e->tick_delta[streams[i]] += nt;
-        rc = score_after_gate(e, k, s);
+        else for (int32_t i = 0; i < rows; ++i) e->tick_delta[streams[i]] += nt;
+        int rc = score_after_gate(e, k, s);
         if (rc) return rc;
         e->push_seq += 1;
     }
-    return finish_push(e, s);
+    return EWK_OK;
 }
 
 int ewk_push(ewk_engine* e, const float* pcm, int64_t stride, int32_t flags) {
@@ -479,6 +518,230 @@ int ewk_push_streams_pcm16(ewk_engine* e, const int32_t* streams, int32_t n, con
     return push_impl(e, pcm, stride, tick_stride, n_ticks, flags, true, streams, n);
 }
 
+// ---------------------------------------------------------------- packet ingest
+static int fail_chunk_plan(ChunkPlanError err, int32_t bad, int32_t in_block, const int32_t* pending,
+                           const int32_t* counts) {
+    switch (err) {
+        case kChunkPlanPending:
+            return fail(EWK_EINVAL, "pending[" + std::to_string(bad) + "] = " + std::to_string(pending[bad]) +
+                                        " is outside [0, " + std::to_string(in_block) + ")");
+        case kChunkPlanCount:
+            return fail(EWK_EINVAL, "counts[" + std::to_string(bad) + "] = " + std::to_string(counts[bad]) +
+                                        " is outside [0, " + std::to_string((int64_t)EWK_CHUNK_MAX_TICKS * in_block) +
+                                        "] (EWK_CHUNK_MAX_TICKS input blocks of " + std::to_string(in_block) + " samples)");
+        case kChunkPlanGroups:
+            return fail(EWK_EINVAL, "the plan has " + std::to_string(bad) + " groups, group_cap holds fewer");
+        default:
+            return fail(EWK_EINVAL, "in_block must be positive, n and group_cap >= 0 and no array NULL");
+    }
+}
+
+int ewk_chunk_plan(int32_t in_block, int32_t n, const int32_t* pending, const int32_t* counts, int32_t* ticks,
+                   int32_t* new_pending, int32_t* order, int32_t* n_ticking, int32_t* group_ticks, int32_t* group_first,
+                   int32_t group_cap, int32_t* n_groups) {
+    int32_t bad = -1;
+    const ChunkPlanError err = chunk_plan(in_block, n, pending, counts, ticks, new_pending, order, n_ticking,
+                                          group_ticks, group_first, group_cap, n_groups, &bad);
+    return err == kChunkPlanOk ? EWK_OK : fail_chunk_plan(err, bad, in_block, pending, counts);
+}
+
+int ewk_stream_pending(ewk_engine* e, const int32_t* streams, int32_t n, int32_t* out) {
+    if (!e || !out) return fail(EWK_EINVAL, "NULL argument");
+    if (n < 0 || n > e->n_streams)
+        return fail(EWK_EINVAL, "n must be in [0, " + std::to_string(e->n_streams) + "]");
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t s = streams ? streams[i] : i;
+        if (s < 0 || s >= e->n_streams) return fail_stream_index(e, i, s);
+    }
+    for (int32_t i = 0; i < n; ++i) out[i] = e->chunk_pending.empty() ? 0 : e->chunk_pending[streams ? streams[i] : i];
+    return EWK_OK;
+}
+
+constexpr int64_t kChunkAlign = 32;   // bytes: a group's first tick row, and a staged chunk's phase (copy_span's widest unit)
+
+// What the first chunk push allocates: the pending mirror, the descriptor staging (pinned and on
+// the device, fixed size) and the carry rows -- those again when a larger input block has been set.
+static int ensure_chunk_state(ewk_engine* e, int64_t in_block, hipStream_t s) {
+    const size_t n = (size_t)e->n_streams;
+    const size_t stage_bytes = n * (sizeof(ChunkDesc) + sizeof(int32_t));
+    if (!e->h_chunk) {
+        HIP_TRY(hipHostMalloc((void**)&e->h_chunk, stage_bytes, hipHostMallocDefault));
+        HIP_TRY(hipEventCreateWithFlags(&e->h_chunk_free, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(e->h_chunk_free, s));
+    }
+    HIP_TRY(e->d_chunk.reserve(stage_bytes));
+    const size_t carry_bytes = n * (size_t)in_block * e->ring_es;
+    if (carry_bytes > e->chunk_carry.cap) {   // (nothing is pending: a new rate drops it)
+        HIP_TRY(hipStreamSynchronize(s));
+        HIP_TRY(e->chunk_carry.reserve(carry_bytes));
+    }
+    if (e->chunk_pending.empty()) e->chunk_pending.assign(n, 0);
+    return EWK_OK;
+}
+
+// Host chunks, packed into the pinned staging and sent with one copy; chunk i then starts at
+// d[i].src of the device staging.  A chunk is placed at the 16-byte phase of the samples it
+// follows in its stream's block, so the assembly kernel's loads and stores agree in phase.
+static int stage_host_chunks(ewk_engine* e, const void* pcm, bool pcm16, const int64_t* offsets, const int32_t* counts,
+                             const int32_t* pending, int32_t n, int64_t* src_at, const void** d_src, hipStream_t s) {
+    const size_t es = pcm16 ? sizeof(int16_t) : sizeof(float);
+    const int64_t unit = kChunkAlign / (int64_t)es;   // samples
+    int64_t total = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        if (counts[i] == 0) {
+            src_at[i] = 0;
+            continue;
+        }
+        src_at[i] = (total + unit - 1) / unit * unit + pending[i] % unit;
+        total = src_at[i] + counts[i];
+    }
+    *d_src = e->push_stage.p;
+    if (total == 0) return EWK_OK;
+    if (e->h_stage_free) HIP_TRY(hipEventSynchronize(e->h_stage_free));   // previous DMA done
+    if ((size_t)total > e->h_stage_cap) {
+        if (e->h_stage) HIP_TRY(hipHostFree(e->h_stage));
+        e->h_stage = nullptr;
+        e->h_stage_cap = 0;
+        HIP_TRY(hipHostMalloc((void**)&e->h_stage, (size_t)total * sizeof(float), hipHostMallocDefault));   // >= es bytes each
+        e->h_stage_cap = (size_t)total;
+    }
+    if (!e->h_stage_free) HIP_TRY(hipEventCreateWithFlags(&e->h_stage_free, hipEventDisableTiming));
+    unsigned char* h = reinterpret_cast<unsigned char*>(e->h_stage);
+    int64_t end = 0;   // (the gaps are copied too: defined bytes)
+    for (int32_t i = 0; i < n; ++i) {
+        if (counts[i] == 0) continue;
+        memset(h + end * es, 0, (size_t)(src_at[i] - end) * es);
+        memcpy(h + src_at[i] * es, static_cast<const unsigned char*>(pcm) + offsets[i] * es, (size_t)counts[i] * es);
+        end = src_at[i] + counts[i];
+    }
+    if ((size_t)total > e->push_stage.cap) {
+        HIP_TRY(hipStreamSynchronize(s));   // an earlier launch may still read the old buffer
+        HIP_TRY(e->push_stage.reserve((size_t)total));
+    }
+    HIP_TRY(hipMemcpyAsync(e->push_stage.p, e->h_stage, (size_t)total * es, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(e->h_stage_free, s));
+    *d_src = e->push_stage.p;
+    return EWK_OK;
+}
+
+static int push_chunks_impl(ewk_engine* e, const int32_t* streams, int32_t n, const void* pcm, int64_t n_pcm,
+                            const int64_t* offsets, const int32_t* counts, int32_t flags, bool pcm16) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (e->n_streams <= 0) return fail(EWK_EINVAL, "engine has no streams");
+    int rc = check_stream_list(e, streams, n);   // (everything is validated before anything is enqueued or changed)
+    if (rc) return rc;
+    if (!offsets || !counts) return fail(EWK_EINVAL, "offsets or counts is NULL");
+    if (n_pcm < 0) return fail(EWK_EINVAL, "n_pcm must be >= 0");
+    if (!pcm && n_pcm > 0) return fail(EWK_EINVAL, "pcm is NULL");
+    if (!pcm16 && e->ring_es == sizeof(int16_t))
+        return fail(EWK_EINVAL, "an int16 ring (EWK_RING_I16) takes PCM16 chunks (ewk_push_chunks_pcm16)");
+    const int32_t in_block = e->rs_on ? e->rs_in_block : e->cfg.block;
+    if (in_block > 0x7fffffff / (EWK_CHUNK_MAX_TICKS + 1))
+        return fail(EWK_EINVAL, "the input block is too large for chunk pushes");
+    // the plan: pending, ticks, new pending, order and chunk sources, n ints each (src_at: int64)
+    e->chunk_plan_buf.resize((size_t)n * 6 + 2);
+    int32_t* pend = e->chunk_plan_buf.data();
+    int32_t *ticks = pend + n, *new_pend = ticks + n, *order = new_pend + n;
+    int64_t* src_at = reinterpret_cast<int64_t*>(order + n + (n & 1));
+    for (int32_t i = 0; i < n; ++i) pend[i] = e->chunk_pending.empty() ? 0 : e->chunk_pending[streams[i]];
+    int32_t group_ticks[EWK_CHUNK_MAX_TICKS], group_first[EWK_CHUNK_MAX_TICKS + 1], n_ticking = 0, n_groups = 0, bad = -1;
+    const ChunkPlanError err = chunk_plan(in_block, n, pend, counts, ticks, new_pend, order, &n_ticking, group_ticks,
+                                          group_first, EWK_CHUNK_MAX_TICKS, &n_groups, &bad);
+    if (err != kChunkPlanOk) return fail_chunk_plan(err, bad, in_block, pend, counts);
+    for (int32_t i = 0; i < n; ++i)
+        if (offsets[i] < 0 || offsets[i] > n_pcm - counts[i])
+            return fail(EWK_EINVAL, "chunk " + std::to_string(i) + " (offsets[" + std::to_string(i) + "] = " +
+                                        std::to_string(offsets[i]) + ", counts[" + std::to_string(i) + "] = " +
+                                        std::to_string(counts[i]) + ") is outside pcm[0, " + std::to_string(n_pcm) + ")");
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    rc = desynchronise(e, s);
+    if (rc == EWK_OK) rc = ensure_chunk_state(e, in_block, s);
+    if (rc) return rc;
+    // the tick rows: group g contiguous, row stride ticks_g * in_block, its base aligned
+    const int64_t row_unit = kChunkAlign / (int64_t)e->ring_es;
+    int64_t group_base[EWK_CHUNK_MAX_TICKS], asm_total = 0;
+    for (int32_t g = 0; g < n_groups; ++g) {
+        group_base[g] = (asm_total + row_unit - 1) / row_unit * row_unit;
+        asm_total = group_base[g] + (int64_t)(group_first[g + 1] - group_first[g]) * group_ticks[g] * in_block;
+    }
+    if ((size_t)asm_total * e->ring_es > e->chunk_asm.cap) {
+        HIP_TRY(hipStreamSynchronize(s));   // an earlier gate launch may still read the old buffer
+        HIP_TRY(e->chunk_asm.reserve((size_t)asm_total * e->ring_es));
+    }
+    const void* d_src = pcm;
+    if (flags & EWK_PUSH_DEVICE) {
+        for (int32_t i = 0; i < n; ++i) src_at[i] = offsets[i];
+    } else {
+        rc = stage_host_chunks(e, pcm, pcm16, offsets, counts, pend, n, src_at, &d_src, s);
+        if (rc) return rc;
+    }
+    // descriptors: the ticking chunks in plan order (the gate's index lists follow it), then the
+    // appending ones; a chunk without samples needs none
+    HIP_TRY(hipEventSynchronize(e->h_chunk_free));   // the previous push's descriptors have left the staging
+    ChunkDesc* h_desc = reinterpret_cast<ChunkDesc*>(e->h_chunk);
+    int32_t* h_list = reinterpret_cast<int32_t*>(e->h_chunk + (size_t)e->n_streams * sizeof(ChunkDesc));
+    int32_t n_desc = 0;
+    for (int32_t g = 0; g < n_groups; ++g)
+        for (int32_t k = group_first[g]; k < group_first[g + 1]; ++k) {
+            const int32_t i = order[k];
+            const int64_t row = group_base[g] + (int64_t)(k - group_first[g]) * group_ticks[g] * in_block;
+            h_desc[n_desc++] = ChunkDesc{src_at[i], row, streams[i], counts[i], pend[i], 0};
+            h_list[k] = streams[i];
+        }
+    for (int32_t i = 0; i < n; ++i)
+        if (ticks[i] == 0 && counts[i] > 0) h_desc[n_desc++] = ChunkDesc{src_at[i], 0, streams[i], counts[i], pend[i], 0};
+    if (n_desc == 0) return EWK_OK;   // no samples at all
+    unsigned char* d_stage = e->d_chunk.p;
+    const int32_t* d_list = reinterpret_cast<const int32_t*>(d_stage + (size_t)e->n_streams * sizeof(ChunkDesc));
+    HIP_TRY(hipMemcpyAsync(d_stage, h_desc, (size_t)n_desc * sizeof(ChunkDesc), hipMemcpyHostToDevice, s));
+    if (n_ticking)
+        HIP_TRY(hipMemcpyAsync(const_cast<int32_t*>(d_list), h_list, (size_t)n_ticking * sizeof(int32_t),
+                               hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(e->h_chunk_free, s));
+    ChunkArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = d_src;
+    a.out = e->chunk_asm.p;
+    a.carry = e->chunk_carry.p;
+    a.desc = reinterpret_cast<const ChunkDesc*>(d_stage);
+    a.n = n_desc;
+    a.in_block = in_block;
+    a.max_ticks = n_groups ? group_ticks[n_groups - 1] : 1;
+    a.src16 = pcm16 ? 1 : 0;
+    a.out16 = e->ring_es == sizeof(int16_t) ? 1 : 0;
+    {
+        ProfScope ps(e, 4, s);
+        HIP_TRY(launch_chunk_assemble(a, s));
+    }
+    for (int32_t i = 0; i < n; ++i) {
+        int32_t& p = e->chunk_pending[streams[i]];
+        e->chunk_pending_n += (new_pend[i] > 0) - (p > 0);
+        p = new_pend[i];
+    }
+    if (n_groups == 0) return EWK_OK;   // nobody ticks: the assembly alone (a poll finds the banks as they were)
+    // the plan's ticking streams on the host, for the tick mirror (h_list is the next push's to overwrite)
+    for (int32_t k = 0; k < n_ticking; ++k) order[k] = streams[order[k]];
+    for (int32_t g = 0; g < n_groups; ++g) {
+        const int32_t first = group_first[g], rows = group_first[g + 1] - first, nt = group_ticks[g];
+        TickSrc src{e->chunk_asm.p + group_base[g] * e->ring_es, a.out16 != 0, (int64_t)nt * in_block, in_block};
+        if (e->rs_on) rc = resample_ticks(e, &src, rows, nt, d_list + first, s);
+        if (rc == EWK_OK) rc = gate_ticks(e, src, rows, nt, d_list + first, order + first, s);
+        if (rc) return rc;
+    }
+    return finish_push(e, s);
+}
+
+int ewk_push_chunks(ewk_engine* e, const int32_t* streams, int32_t n, const float* pcm, int64_t n_pcm,
+                    const int64_t* offsets, const int32_t* counts, int32_t flags) {
+    return push_chunks_impl(e, streams, n, pcm, n_pcm, offsets, counts, flags, false);
+}
+
+int ewk_push_chunks_pcm16(ewk_engine* e, const int32_t* streams, int32_t n, const int16_t* pcm, int64_t n_pcm,
+                          const int64_t* offsets, const int32_t* counts, int32_t flags) {
+    return push_chunks_impl(e, streams, n, pcm, n_pcm, offsets, counts, flags, true);
+}
+
 int ewk_reset_stream_list(ewk_engine* e, const int32_t* streams, int32_t n) {
     if (!e) return fail(EWK_EINVAL, "engine is NULL");
     if (e->n_streams <= 0) return fail(EWK_EINVAL, "engine has no streams");
@@ -508,6 +771,7 @@ int ewk_reset_stream_list(ewk_engine* e, const int32_t* streams, int32_t n) {
     a.lsn_st = e->d_lsn_st.p;
     HIP_TRY(launch_reset_list(a, s));
     for (int32_t i = 0; i < n; ++i) e->tick_delta[streams[i]] = -e->tick;
+    for (int32_t i = 0; i < n; ++i) e->drop_pending(streams[i]);
     return EWK_OK;
 }
 

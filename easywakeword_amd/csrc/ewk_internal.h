@@ -296,6 +296,34 @@ hipError_t launch_resample(const ResampleArgs& a, hipStream_t s);
 // has read the old one (stream order); fresh: nullptr or a.fresh
 hipError_t launch_resample_save(const ResampleArgs& a, float* hist, uint8_t* fresh, hipStream_t s);
 
+// Packet ingest (ewk_chunks.hip): one launch per ewk_push_chunks* call re-blocks the call's
+// chunks.  Stream d.stream holds d.pending < in_block samples in its carry row
+// carry[d.stream * in_block ..]; its chunk src[d.src .. d.src + d.count) follows them.  With
+// T = (d.pending + d.count) / in_block >= 1 the first T * in_block samples of carry ++ chunk
+// become the tick rows out[d.row + t * in_block ..], t < T, and the rest (from the chunk's tail
+// alone) the new carry; with T = 0 the chunk is appended to the carry at d.pending.  Carry and
+// rows have the ring's sample type, PCM16 into float is decoded as x / 32768.
+struct ChunkDesc {
+    int64_t src;       // first sample of the chunk (elements of the source type)
+    int64_t row;       // first sample of the chunk's tick row 0 in `out` (elements; unused without a tick)
+    int32_t stream;
+    int32_t count;
+    int32_t pending;   // before the push
+    int32_t pad;
+};
+static_assert(sizeof(ChunkDesc) == 32, "chunk descriptors are staged as bytes");
+struct ChunkArgs {
+    const void* src;          // float32, or int16 with src16
+    void* out;                // tick rows: float32, or int16 with out16
+    void* carry;              // [n_streams][in_block], the type of out
+    const ChunkDesc* desc;    // [n]
+    int32_t n;
+    int32_t in_block;
+    int32_t max_ticks;        // the largest T of the call (the launch's grid.y, at least 1)
+    int32_t src16, out16;     // (float32 into int16 does not exist: an int16 ring takes PCM16)
+};
+hipError_t launch_chunk_assemble(const ChunkArgs& a, hipStream_t s);
+
 // ewk_gather.hip: positives compaction (scratch: 2 * compact_blocks(n) int32)
 int compact_blocks(int32_t n);
 hipError_t launch_compact_positives(const double* score, const uint8_t* match, int32_t n, int64_t first_id,

@@ -556,6 +556,58 @@ class StreamEngine(Engine):
         check(self._lib.ewk_stream_ticks(self._h, _lib.i32ptr(s), s.size, _lib.i64ptr(out)))
         return out
 
+    # -- packet ingest: any number of samples per stream ---------------------------
+    def _push_chunks(self, fn, streams, chunks, dtype) -> None:
+        s = self._stream_list(streams)
+        parts = [np.ascontiguousarray(c, dtype=dtype).reshape(-1) for c in chunks]
+        if len(parts) != s.size:
+            raise ValueError(f"{s.size} streams listed, {len(parts)} chunks given")
+        counts = np.array([p.size for p in parts], np.int32)
+        offsets = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)[:-1]]).astype(np.int64)
+        pcm = np.concatenate(parts) if parts else np.zeros(0, dtype)
+        check(fn(self._h, _lib.i32ptr(s), s.size, pcm.ctypes.data_as(C.c_void_p), pcm.size, _lib.i64ptr(offsets),
+                 _lib.i32ptr(counts), 0))
+
+    def push_chunks(self, streams, chunks) -> None:
+        """Any number of samples per stream: chunks[i], a 1-D float32 array (host) of any length up
+        to EWK_CHUNK_MAX_TICKS * input_block, holds the next input samples of stream streams[i].
+        The engine keeps each stream's unfinished block on the device (stream_pending) and steps
+        the gate for a stream whenever a whole block has arrived: its events are those of an engine
+        fed the same samples in blocks, however they were cut.  ValueError, with nothing delivered,
+        for a bad list or a chunk that is too long."""
+        self._push_chunks(self._lib.ewk_push_chunks, streams, chunks, np.float32)
+
+    def push_chunks_pcm16(self, streams, chunks) -> None:
+        """push_chunks with int16 PCM chunks (decoded on the device; an int16 ring stores them as they are)."""
+        self._push_chunks(self._lib.ewk_push_chunks_pcm16, streams, chunks, np.int16)
+
+    def push_chunks_device(self, streams, ptr: int, n_pcm: int, offsets, counts, pcm16: bool = False) -> None:
+        """Device-resident chunks: chunk i is the counts[i] samples at ptr + es * offsets[i] (es = 4,
+        or 2 with pcm16=True) of a buffer of n_pcm samples; any offset, aligned or not.  `streams`,
+        `offsets` and `counts` stay host lists."""
+        s = self._stream_list(streams)
+        o = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        c = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+        if o.size != s.size or c.size != s.size:
+            raise ValueError(f"{s.size} streams listed, {o.size} offsets and {c.size} counts given")
+        fn = self._lib.ewk_push_chunks_pcm16 if pcm16 else self._lib.ewk_push_chunks
+        check(fn(self._h, _lib.i32ptr(s), s.size, C.c_void_p(ptr), int(n_pcm), _lib.i64ptr(o), _lib.i32ptr(c),
+                 _lib.EWK_PUSH_DEVICE))
+
+    def stream_pending(self, streams=None) -> np.ndarray:
+        """Samples of an unfinished block each listed stream (None: all) holds on the device
+        (int32, in [0, input_block); host bookkeeping, no wait)."""
+        if streams is None:
+            out = np.zeros(self.n_streams, np.int32)
+            check(self._lib.ewk_stream_pending(self._h, None, self.n_streams, _lib.i32ptr(out)))
+            return out
+        s = np.ascontiguousarray(streams, dtype=np.int32).reshape(-1)
+        out = np.zeros(s.size, np.int32)
+        if s.size > self.n_streams:
+            raise ValueError(f"{s.size} streams listed, the engine has {self.n_streams}")
+        check(self._lib.ewk_stream_pending(self._h, _lib.i32ptr(s), s.size, _lib.i32ptr(out)))
+        return out
+
     def assign_stream_words(self, streams, words) -> None:
         """With the stream bank on (set_stream_bank): stream streams[i] listens for word words[i]
         from the next push on; earlier events keep the word they were scored with."""

@@ -179,7 +179,8 @@ class WordMatcher:
 class SoundBuffer:
     """The reference SoundBuffer protocol (wakeword.py:405-517) on a 1-stream
     GPU engine.  ``source`` replaces the PortAudio InputStream; ``pump()``
-    delivers one callback block (what PortAudio does every 0.1 s)."""
+    delivers one callback block (what PortAudio does every 0.1 s); a source whose reads are not
+    ticks (ArraySource(read_sizes=), MicSource(blocksize=0)) is re-blocked on the device."""
 
     FREQUENCY = FREQUENCY
     MIN_THRESHOLD = 0.005
@@ -197,11 +198,18 @@ class SoundBuffer:
         rate = int(getattr(source, "rate", FREQUENCY) or FREQUENCY)
         if rate != FREQUENCY:
             self.engine.set_input_rate(rate)
+        self._chunked = False   # a read of another length than a tick has gone through push_chunks
         self.source.start()
 
     def pump(self) -> np.ndarray:
         blk = self.source.read()
-        self.engine.push(np.asarray(blk, np.float32).reshape(1, -1))
+        a = np.asarray(blk, np.float32).reshape(1, -1)
+        # a tick goes through push as ever -- unless samples of an earlier packet are pending, which it must follow
+        if a.shape[1] == self.engine.input_block and not (self._chunked and self.engine.stream_pending([0])[0]):
+            self.engine.push(a)
+        else:   # a packet of another length than a tick: re-blocked on the device
+            self.engine.push_chunks([0], [a[0]])
+            self._chunked = True
         return blk
 
     def start(self) -> None:

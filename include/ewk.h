@@ -325,6 +325,64 @@ int ewk_reset_stream_list(ewk_engine* e, const int32_t* streams, int32_t n);
  * tick plus a per-stream delta, 8 bytes per stream, allocated when the engine desynchronises.) */
 int ewk_stream_ticks(ewk_engine* e, const int32_t* streams, int32_t n, int64_t* out);
 
+/* ---- packet ingest: any number of samples per stream ---------------------------- */
+/* Sources do not deliver whole ticks: an RTP or WebRTC client sends 10, 20, 30 or 60 ms packets, a
+ * decoder hands out what it decoded.  The calls below take, for a list of streams, any number of
+ * samples each, and re-block them on the device: every stream keeps the samples of its unfinished
+ * block (`pending`, in [0, input_block)) in a carry row in device memory, and the gate steps for a
+ * stream whenever a whole block has arrived.  Stream s produces exactly what a one-stream engine
+ * produces when fed the same samples cut into blocks -- every event field and the score's bits --
+ * however the samples were split into chunks.
+ *
+ * Chunk i is pcm[offsets[i] .. offsets[i] + counts[i]): the next counts[i] input samples of stream
+ * streams[i], at the input rate when one is set (ewk_set_input_rate), else at 16 kHz.  streams,
+ * offsets and counts are always host arrays (`streams` as for ewk_push_streams); pcm is host
+ * memory, or device memory with EWK_PUSH_DEVICE; n_pcm is its length in samples.  counts[i] may be
+ * 0, and at most EWK_CHUNK_MAX_TICKS * input_block.  Any sample offset is legal: a float row need
+ * not be 16-byte aligned, an int16 offset may be odd (the kernel copies 16 bytes at a time where
+ * source and destination agree in phase, as host chunks always do, and narrower at the edges).
+ * The push makes (pending + counts[i]) / input_block gate ticks for the stream, taken in order
+ * from its carry followed by the chunk, and leaves (pending + counts[i]) % input_block samples in
+ * the carry.  Streams that make the same number of ticks share their gate launches, which are cut
+ * and scored as for ewk_push_streams; ewk_stream_ticks follows the ticks made.  A push in which no
+ * stream completes a block only moves samples.
+ *
+ * The carry has the ring's sample type.  PCM16 chunks into a float ring are decoded as x / 32768
+ * when they are appended (exact: the stream equals one pushed with ewk_push_pcm16); float chunks
+ * into an int16 ring are refused, as float pushes are.
+ *
+ * Everything is validated on the host before anything is enqueued or changed -- the list rules of
+ * ewk_push_streams, every count in range, 0 <= offsets[i] and offsets[i] + counts[i] <= n_pcm --
+ * else EWK_EINVAL, naming the offending entry.  The first chunk push desynchronises the engine, as
+ * a subset push does, and allocates the carry (input_block samples per stream: 6,400 bytes for a
+ * float ring at block 1600, 3,200 for an int16 ring), 4 bytes of host mirror per stream and the
+ * staging of the descriptors; the buffer of the assembled ticks grows to the largest push.  An
+ * engine that is never chunk-pushed allocates none of it.
+ *
+ * A tick push to a stream with pending samples would put its audio out of order: ewk_push_streams*
+ * on such a stream, and ewk_push* while any stream has pending samples, return EWK_EINVAL naming
+ * the stream and its pending count.  ewk_reset_streams, ewk_reset_stream_list (for the streams it
+ * lists) and ewk_set_input_rate (the unit changes) drop the pending samples. */
+#define EWK_CHUNK_MAX_TICKS 64
+int ewk_push_chunks(ewk_engine* e, const int32_t* streams, int32_t n, const float* pcm, int64_t n_pcm,
+                    const int64_t* offsets, const int32_t* counts, int32_t flags);
+int ewk_push_chunks_pcm16(ewk_engine* e, const int32_t* streams, int32_t n, const int16_t* pcm, int64_t n_pcm,
+                          const int64_t* offsets, const int32_t* counts, int32_t flags);
+/* Samples each listed stream holds in its carry (0 on an engine that was never chunk-pushed).
+ * streams NULL: streams 0..n-1.  Reads the host mirror: no device access, no wait. */
+int ewk_stream_pending(ewk_engine* e, const int32_t* streams, int32_t n, int32_t* out);
+/* The planning step of a chunk push as a pure host function: no engine, no device.  For chunk i of
+ * counts[i] samples to a stream holding pending[i] in [0, in_block): ticks[i] = (pending[i] +
+ * counts[i]) / in_block and new_pending[i] = (pending[i] + counts[i]) % in_block.  order: the
+ * *n_ticking chunks with ticks >= 1, sorted by (ticks, position in the call).  Groups: the runs of
+ * equal ticks in order -- group g is order[group_first[g] .. group_first[g + 1]) and makes
+ * group_ticks[g] ticks; group_ticks holds group_cap entries, group_first group_cap + 1 (at most
+ * EWK_CHUNK_MAX_TICKS groups exist).  EWK_EINVAL, with nothing written, for in_block < 1, a NULL
+ * array, a pending or count out of range, or more groups than group_cap. */
+int ewk_chunk_plan(int32_t in_block, int32_t n, const int32_t* pending, const int32_t* counts,
+                   int32_t* ticks, int32_t* new_pending, int32_t* order, int32_t* n_ticking,
+                   int32_t* group_ticks, int32_t* group_first, int32_t group_cap, int32_t* n_groups);
+
 /* ---- level 1 + 2 against many references: the stream bank ---------------------- */
 /* From the next push on, every gated event of stream s is scored against the templates of word
  * stream_word[s] of the engine's bank (NULL: word 0 for every stream) instead of the single
@@ -546,7 +604,8 @@ int ewk_input_rate_info(ewk_engine* e, int32_t* in_rate, int32_t* in_block, int3
  * without brackets.  ewk_profile_read resolves them (synchronizing) and returns
  * the summed device time and launch count per kernel family, then clears.
  * kind: 0 = fp32 MFCC scorer (k_score_f32), 1 = fp64 re-scorer, 2 = gate ticks,
- * 3 = resampler launches (ewk_resample, and the resample + history save of a push). */
+ * 3 = resampler launches (ewk_resample, and the resample + history save of a push),
+ * 4 = the assembly launch of a chunk push (ewk_push_chunks*). */
 int ewk_profile_enable(ewk_engine* e, int32_t on);
 int ewk_profile_read(ewk_engine* e, int32_t kind, double* total_ms, int64_t* launches);
 
