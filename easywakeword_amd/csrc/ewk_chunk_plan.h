@@ -1,4 +1,4 @@
-// ewk_chunk_plan.h -- the planning step of a chunk push (ewk_push_chunks, ewk_chunk_plan).
+// ewk_chunk_plan.h -- the planning and layout steps of a chunk push (ewk_push_chunks, ewk_chunk_plan).
 // Pure host code without HIP: a host compiler builds it alone (tests/test_chunk_plan.py runs it
 // under the address and undefined-behaviour sanitizers).
 //
@@ -77,6 +77,36 @@ inline ChunkPlanError chunk_plan(int32_t in_block, int32_t n, const int32_t* pen
         if (t > 0) order[first[t]++] = i;
     }
     return kChunkPlanOk;
+}
+
+// The layout of a planned push, in samples.  A group's first tick row and a staged chunk's phase
+// are aligned to kChunkAlign bytes (copy_span's widest unit): `unit` is that many samples.
+constexpr int64_t kChunkAlign = 32;
+
+// Host chunks packed into one staging buffer: src_at[i], where chunk i starts -- each non-empty
+// chunk at the next unit-aligned position plus pending[i] % unit, the phase of the samples it
+// follows in its stream's block, so the assembly kernel's loads and stores agree in phase (an
+// empty chunk: 0).  Returns the samples the buffer holds, the gaps included.
+inline int64_t chunk_stage_layout(int64_t unit, int32_t n, const int32_t* pending, const int32_t* counts,
+                                  int64_t* src_at) {
+    int64_t total = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        src_at[i] = counts[i] == 0 ? 0 : (total + unit - 1) / unit * unit + pending[i] % unit;
+        if (counts[i] > 0) total = src_at[i] + counts[i];
+    }
+    return total;
+}
+
+// The tick rows: group g contiguous from group_base[g], a multiple of row_unit, one row of
+// group_ticks[g] * in_block samples per member.  Returns the end of the last group.
+inline int64_t chunk_row_layout(int64_t row_unit, int32_t in_block, int32_t n_groups, const int32_t* group_ticks,
+                                const int32_t* group_first, int64_t* group_base) {
+    int64_t total = 0;
+    for (int32_t g = 0; g < n_groups; ++g) {
+        group_base[g] = (total + row_unit - 1) / row_unit * row_unit;
+        total = group_base[g] + (int64_t)(group_first[g + 1] - group_first[g]) * group_ticks[g] * in_block;
+    }
+    return total;
 }
 
 }  // namespace ewk

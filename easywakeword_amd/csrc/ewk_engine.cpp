@@ -139,18 +139,13 @@ void ewk_destroy(ewk_engine* e) {
     (void)hipSetDevice(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     if (e->sstream) (void)hipStreamSynchronize(e->sstream);
-    // what no DevBuf owns (those go with `delete e`, after the streams above are idle)
+    // what no DevBuf or PinnedStage owns: those go with `delete e` below -- by then the device is
+    // set and the streams are idle and destroyed, so nothing can still read what they free
     (void)hipFree(e->d_tab);
     (void)hipFree(e->d_tab64);
     (void)hipFree(e->d_tmpl);
     (void)hipFree(e->d_work);
     (void)hipFree(e->d_compact);
-    if (e->h_ids) (void)hipHostFree(e->h_ids);
-    if (e->h_ids_free) (void)hipEventDestroy(e->h_ids_free);
-    if (e->h_lsn_stage) (void)hipHostFree(e->h_lsn_stage);
-    if (e->h_lsn_free) (void)hipEventDestroy(e->h_lsn_free);
-    if (e->h_chunk) (void)hipHostFree(e->h_chunk);
-    if (e->h_chunk_free) (void)hipEventDestroy(e->h_chunk_free);
     (void)hipFree(e->d_ring);
     (void)hipFree(e->d_brms);
     (void)hipFree(e->d_sorted);
@@ -158,9 +153,7 @@ void ewk_destroy(ewk_engine* e) {
     (void)hipFree(e->d_st);
     (void)hipFree(e->d_events);
     (void)hipFree(e->d_evc);
-    if (e->h_stage) (void)hipHostFree(e->h_stage);
     if (e->h_poll) (void)hipHostFree(e->h_poll);
-    if (e->h_stage_free) (void)hipEventDestroy(e->h_stage_free);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     if (e->cstream) (void)hipStreamDestroy(e->cstream);
     if (e->sstream) (void)hipStreamDestroy(e->sstream);

@@ -1,5 +1,6 @@
 // ewk_engine.h -- the engine behind the C ABI (include/ewk.h): its state, and the helpers its
-// sources share.  Internal: only ewk_engine.cpp and ewk_engine_{score,stream,resample}.cpp include it.
+// sources share.  Internal: only ewk_engine.cpp and ewk_engine_{score,resample} (batch side),
+// ewk_engine_{stream,chunks,assign,poll}.cpp (streaming side) include it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "ewk_chunk_plan.h"
 #include "ewk_gate.h"
 #include "ewk_internal.h"
 
@@ -48,6 +50,46 @@ struct DevBuf {
         p = nullptr;
         cap = 0;
     }
+};
+
+// Pinned host memory on its way to the device, and the event that says its last DMA has left it:
+// reserve(), fill, hipMemcpyAsync on s, sent(s).
+struct PinnedStage {
+    unsigned char* p = nullptr;
+    size_t cap = 0;   // bytes
+    hipEvent_t done = nullptr;
+    bool recorded = false;
+    PinnedStage() = default;
+    PinnedStage(const PinnedStage&) = delete;
+    PinnedStage& operator=(const PinnedStage&) = delete;
+    ~PinnedStage() {
+        (void)hipHostFree(p);
+        if (done) (void)hipEventDestroy(done);
+    }
+    hipError_t wait() { return recorded ? hipEventSynchronize(done) : hipSuccess; }
+    hipError_t reserve(size_t bytes) {   // at least `bytes`, nothing in flight out of them: the caller's to fill
+        hipError_t err = wait();
+        if (err == hipSuccess && !done) err = hipEventCreateWithFlags(&done, hipEventDisableTiming);
+        if (err != hipSuccess || bytes <= cap) return err;
+        (void)hipHostFree(p);
+        p = nullptr;
+        err = hipHostMalloc((void**)&p, bytes, hipHostMallocDefault);
+        cap = err == hipSuccess ? bytes : 0;
+        return err;
+    }
+    hipError_t sent(hipStream_t s) { return recorded = true, hipEventRecord(done, s); }
+    template <typename T>
+    T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+// A chunk push's plan and layout (ewk_chunk_plan.h), kept between pushes for its storage.
+struct ChunkPlan {
+    std::vector<int32_t> pending, ticks, new_pending, order;   // [n], per listed stream (order: n_ticking used)
+    std::vector<int64_t> src_at;                               // [n]: chunk i's first sample in the push's source
+    int32_t group_ticks[EWK_CHUNK_MAX_TICKS], group_first[EWK_CHUNK_MAX_TICKS + 1];
+    int64_t group_base[EWK_CHUNK_MAX_TICKS];                   // first tick row of group g in chunk_asm
+    int32_t in_block = 0, n_ticking = 0, n_groups = 0;
+    int64_t asm_total = 0, stage_total = 0;                    // samples: all tick rows; the staged host chunks
 };
 
 constexpr int kWorkInts = 32;          // ewk_engine::d_work
@@ -159,15 +201,13 @@ struct ewk_engine {
     int32_t ticks_per_launch = 32;                  // gate launch length (segments must outlive it in the ring)
     ewk_event* ev_bank(int b) { return d_events + (size_t)b * ev_cap; }
     int32_t* evc_bank(int b) { return d_evc + 4 * b; }
+    ewk::PinnedStage pcm_stage;       // a push's host samples (ticks or chunks) on the way to push_stage
     ewk::DevBuf<float> push_stage;
-    float* h_stage = nullptr;       // pinned host staging for ewk_push / ewk_push_many
     unsigned char* h_poll = nullptr;   // pinned: event counters + the first kPollChunk events
     unsigned char* d_poll = nullptr;   // h_poll's device address (k_bank_mirror writes it)
     // mirror[b]: h_poll's region b holds bank b as of bank_done[b], written by k_bank_mirror
     // after the push's last scoring pass (same stream) -- the poll needs no copies
     bool mirror[2] = {false, false};
-    size_t h_stage_cap = 0;
-    hipEvent_t h_stage_free = nullptr;   // recorded after the last DMA out of h_stage
     int64_t tick = 0;
     // Stream lifecycle (ewk_push_streams / ewk_reset_stream_list).  A lockstep engine has one clock,
     // `tick`.  The first subset push or list reset desynchronises it: stream s has then had
@@ -178,9 +218,8 @@ struct ewk_engine {
     std::vector<int64_t> tick_delta;   // [n_streams] once desynchronised
     std::vector<uint32_t> seen;        // [n_streams]: the epoch of the call that last listed the stream
     uint32_t seen_epoch = 0;
-    int32_t* h_ids = nullptr;          // pinned [2 * n_streams]: an index list (and its words) on the way to d_ids
+    ewk::PinnedStage ids_stage;        // [2 * n_streams] int32: an index list (and its values) on the way to d_ids
     ewk::DevBuf<int32_t> d_ids;        // [2 * n_streams]
-    hipEvent_t h_ids_free = nullptr;   // recorded after the last DMA out of h_ids
     int64_t stream_tick(int32_t s) const { return tick + (desync ? tick_delta[s] : 0); }
     // Detector profiles (ewk_detector_profiles_set): the table as set and on the device, and the
     // profile of every stream (-1: cfg) on the device with its host mirror; both per-stream arrays
@@ -194,18 +233,17 @@ struct ewk_engine {
     // more than one listener: per stream the count, EWK_LISTENERS_MAX table rows and kLsnStates
     // states on the device, count and rows mirrored on the host (row 0 of the mirror is not read:
     // listener 0 is stream_profile[s] and stream_word[s]).  lsn_multi: streams with more than one
-    // listener; the gate runs its listener instantiations only while it is > 0.  lsn_stage: pinned
-    // [n_streams * (1 + 2 * EWK_LISTENERS_MAX)] ints, a call's counts and rows on the way to
-    // d_lsn_stage (the stream list goes through h_ids).
+    // listener; the gate runs its listener instantiations only while it is > 0.  lsn_stage:
+    // [n_streams * (1 + 2 * EWK_LISTENERS_MAX)] ints, a call's rows and counts on the way to
+    // d_lsn_stage (the stream list goes through ids_stage).
     ewk::DevBuf<int32_t> d_lsn_count;          // [n_streams]
     ewk::DevBuf<ewk_listener> d_lsn_tab;       // [n_streams][EWK_LISTENERS_MAX]
     ewk::DevBuf<ewk::LsnState> d_lsn_st;       // [n_streams][kLsnStates]
     std::vector<int32_t> lsn_count;            // [n_streams]; empty: every stream has one listener
     std::vector<ewk_listener> lsn_tab;         // [n_streams][EWK_LISTENERS_MAX]
     int32_t lsn_multi = 0;
-    int32_t* h_lsn_stage = nullptr;
+    ewk::PinnedStage lsn_stage;
     ewk::DevBuf<int32_t> d_lsn_stage;
-    hipEvent_t h_lsn_free = nullptr;           // recorded after the last DMA out of h_lsn_stage
     std::vector<int32_t> stream_word;          // host mirror of sb_word (empty: word 0 everywhere)
     bool listeners_on() const { return !lsn_count.empty(); }
     // Packet ingest (ewk_push_chunks*, ewk_chunks.hip); everything is allocated by the first chunk
@@ -214,14 +252,13 @@ struct ewk_engine {
     // possible while nothing is pending).  chunk_pending: its host mirror, samples held per stream
     // (every device read of a carry row is bounded by it, so dropping samples needs no device
     // work); chunk_pending_n: streams holding any.  chunk_asm: the tick rows of one push, grown to
-    // the largest push so far.  h_chunk -> d_chunk: a push's descriptors ([n_streams] ChunkDesc)
+    // the largest push so far.  chunk_stage -> d_chunk: a push's descriptors ([n_streams] ChunkDesc)
     // followed by its ticking streams in plan order ([n_streams] int32, the gate's index lists).
     ewk::DevBuf<unsigned char> chunk_carry, chunk_asm, d_chunk;
     std::vector<int32_t> chunk_pending;        // [n_streams]; empty: no chunk push yet
     int32_t chunk_pending_n = 0;
-    unsigned char* h_chunk = nullptr;          // pinned
-    hipEvent_t h_chunk_free = nullptr;         // recorded after the last DMA out of h_chunk
-    std::vector<int32_t> chunk_plan_buf;       // a push's plan (ewk_chunk_plan.h), 5 ints per listed stream
+    ewk::PinnedStage chunk_stage;
+    ewk::ChunkPlan chunk_plan;                 // the current push's
     void drop_pending(int32_t s) {
         if (chunk_pending.empty() || chunk_pending[s] == 0) return;
         chunk_pending[s] = 0;
@@ -305,5 +342,32 @@ int fail_word_index(int32_t word, WordOf of, int32_t i, int32_t n_words);
 // ewk_engine_resample.cpp: a push's resample stage -- every tick at *src into rs_out (float32 16 kHz
 // blocks, where *src then points), the history saved for the next push; d_list: ResampleArgs::ids
 int resample_ticks(ewk_engine* e, TickSrc* src, int32_t rows, int32_t n_ticks, const int32_t* d_list, hipStream_t s);
+
+// A device buffer that launches enqueued on s read grows only once s is idle: an earlier launch
+// may still read the old buffer.
+template <typename T>
+int grow_behind(DevBuf<T>& b, size_t n, hipStream_t s) {
+    if (n > b.cap) HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(b.reserve(n));
+    return EWK_OK;
+}
+
+// ewk_engine_stream.cpp: index lists, and the stages that tick and chunk pushes share
+int fail_stream_index(ewk_engine* e, int32_t i, int32_t s);
+int check_stream_list(ewk_engine* e, const int32_t* streams, int32_t n);   // of a call that changes streams
+int check_query_list(ewk_engine* e, const int32_t* streams, int32_t n);    // of a query (NULL: streams 0..n-1)
+int stage_stream_list(ewk_engine* e, const int32_t* streams, const int32_t* vals, int32_t n, hipStream_t s);
+int scatter_assign(ewk_engine* e, ewk::DevBuf<int32_t>& dst, std::vector<int32_t>& mirror, const int32_t* streams,
+                   const int32_t* vals, int32_t n, hipStream_t s);
+int desynchronise(ewk_engine* e, hipStream_t s);
+int send_staged(ewk_engine* e, size_t bytes, hipStream_t s);
+int gate_ticks(ewk_engine* e, const TickSrc& src, int32_t rows, int32_t n_ticks, const int32_t* d_list,
+               const int32_t* streams, hipStream_t s);
+int finish_push(ewk_engine* e, hipStream_t s);
+// ewk_engine_assign.cpp: the per-stream word and profile index arrays, created on s when first needed
+int ensure_stream_words(ewk_engine* e, hipStream_t s);
+int ensure_stream_profile(ewk_engine* e, hipStream_t s);
+// ewk_engine_poll.cpp
+hipError_t ensure_poll_region(ewk_engine* e);
 
 }  // namespace ewk

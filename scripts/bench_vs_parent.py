@@ -3,17 +3,19 @@
 
   tick   scripts/bench_push_streams.py --cases a (the lockstep tick of 8,192 streams without any
          table or list: tick_ms_median and gate_ms_per_launch), and
-  bench  bench.py --gpus 1 --steps 20 --warmup 5 (`value`),
+  bench  bench.py --gpus 1 --steps 20 --warmup 5 (`value`), and
+  chunks scripts/bench_push_chunks.py --cases cd (packet ingest at 8,192 streams: step_ms_median of
+         case c, one block per stream and push, and of case d, five 320-sample packets per tick),
 
 each in a fresh process per tree and round, the order of the two trees swapped every round.
 Acceptance as profiles/engine_split_vs_parent.json: this checkout's median inside the min..max of
 the parent's rounds.  A step that fails or runs past its time limit ends the script at once.
 
-    python scripts/bench_vs_parent.py --parent DIR [--what tick,bench] [--rounds 5] --out FILE
+    python scripts/bench_vs_parent.py --parent DIR [--what tick,bench,chunks] [--rounds 5] --out FILE
 
 DIR holds the parent commit with its own libewk.so built in place (git worktree + python -m
-easywakeword_amd.build there).  An existing FILE is extended: `tick` and `bench` may come from
-two calls.
+easywakeword_amd.build there).  An existing FILE is extended: `tick`, `bench` and `chunks` may
+come from separate calls.
 """
 import argparse
 import json
@@ -64,6 +66,9 @@ def main():
     if "bench" in what:
         for t in trees:
             res[t]["bench_value"] = []
+    if "chunks" in what:
+        for t in trees:
+            res[t]["chunk_c_ms"], res[t]["chunk_d_ms"] = [], []
     for r in range(args.rounds):
         order = ["parent", "new"] if r % 2 == 0 else ["new", "parent"]
         for t in order:
@@ -74,18 +79,24 @@ def main():
             if "bench" in what:
                 d = run_json(trees[t], ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"], 400)
                 res[t]["bench_value"].append(d["value"])
+            if "chunks" in what:
+                d = run_json(trees[t], ["scripts/bench_push_chunks.py", "--cases", "cd"], 240)
+                res[t]["chunk_c_ms"].append(d["step"]["c"]["step_ms_median"])
+                res[t]["chunk_d_ms"].append(d["step"]["d"]["step_ms_median"])
             print(f"round {r} {t} done", flush=True)
+    names = ("tick_ms", "gate_ms", "bench_value", "chunk_c_ms", "chunk_d_ms")
     for t in trees:
-        for name in ("tick_ms", "gate_ms", "bench_value"):
+        for name in names:
             if res[t].get(name):
                 res[t].update(stats(name, res[t][name]))
-    for name in ("tick_ms", "gate_ms", "bench_value"):
+    for name in names:
         if res["new"].get(name) and res["parent"].get(name):
             res[f"{name}_new_median_inside_parent_range"] = bool(
                 res["parent"][f"{name}_min"] <= res["new"][f"{name}_median"] <= res["parent"][f"{name}_max"])
     res["what"] = ("lockstep streaming tick (scripts/bench_push_streams.py --cases a, 8,192 streams, no profile table, "
                    "HIP-event ms per tick, median of 5 rounds x 40 ticks; gate_ms: its gate launch from "
-                   "ewk_profile_read kind 2) and bench.py --gpus 1 --steps 20 --warmup 5 `value`: the parent "
+                   "ewk_profile_read kind 2), bench.py --gpus 1 --steps 20 --warmup 5 `value` and packet ingest "
+                   "(scripts/bench_push_chunks.py --cases cd, step_ms_median of cases c and d): the parent "
                    "commit's build against this one, a fresh process per tree and round, the order swapped every "
                    "round (scripts/bench_vs_parent.py); acceptance: the new build's median inside the min..max of "
                    "the parent's rounds")

@@ -2,7 +2,9 @@
 per chunk, the ticking chunks ordered by (ticks, position), the groups of equal ticks.  Checked
 through the library against a numpy model on fixed and seeded random cases, and once more in a
 stand-alone program built with g++ -fsanitize=address,undefined that replays the same cases (the
-header is HIP-free; nothing of it is loaded into Python).  CPU only."""
+header is HIP-free; nothing of it is loaded into Python).  The same program runs the two layout
+functions of a planned push (chunk_stage_layout, chunk_row_layout: internal, no export), checked
+against numpy models and by their properties.  CPU only."""
 import ctypes as C
 import os
 import shutil
@@ -24,6 +26,31 @@ def model(in_block, pending, counts):
     group_ticks = np.unique(ticks[order])
     first = np.r_[np.searchsorted(ticks[order], group_ticks), len(order)]
     return ticks, new, order, group_ticks, first
+
+
+def stage_model(unit, pending, counts):
+    """chunk_stage_layout: (src_at, total) -- every non-empty chunk at the next multiple of `unit`
+    plus its pending % unit, an empty one at 0."""
+    p, c = np.asarray(pending, np.int64), np.asarray(counts, np.int64)
+    src_at, total = np.zeros(len(c), np.int64), 0
+    for i in np.flatnonzero(c):
+        src_at[i] = -(-total // unit) * unit + p[i] % unit
+        total = int(src_at[i] + c[i])
+    return src_at, total
+
+
+def row_model(row_unit, in_block, group_ticks, first):
+    """chunk_row_layout: (group_base, asm_total) -- group g holds one row of group_ticks[g] * in_block
+    samples per member, from the next multiple of row_unit."""
+    size = np.diff(np.asarray(first, np.int64)) * np.asarray(group_ticks, np.int64) * in_block
+    base, total = np.zeros(len(size), np.int64), 0
+    for g in range(len(size)):
+        base[g] = -(-total // row_unit) * row_unit
+        total = int(base[g] + size[g])
+    return base, total
+
+
+UNITS = (8, 16)     # samples in 32 bytes of float32 and of int16
 
 
 def cases():
@@ -142,18 +169,32 @@ int main() {
             for (int i = 0; i <= ng; ++i) printf(" %%d", gf[i]);
         }
         printf("\n");
+        // the layout of the planned push, a line "L unit total src_at[n] asm_total group_base[ng]" per unit
+        const int units[2] = {8, 16};
+        for (int u = 0; rc == 0 && u < 2; ++u) {
+            std::vector<int64_t> src_at(n), base(ng);
+            long long total = ewk::chunk_stage_layout(units[u], n, pending.data(), counts.data(), src_at.data());
+            long long rows = ewk::chunk_row_layout(units[u], in_block, ng, gt.data(), gf.data(), base.data());
+            printf("L %%d %%lld", units[u], total);
+            for (int i = 0; i < n; ++i) printf(" %%lld", (long long)src_at[i]);
+            printf(" %%lld", rows);
+            for (int i = 0; i < ng; ++i) printf(" %%lld", (long long)base[i]);
+            printf("\n");
+        }
     }
     return 0;
 }
 '''
 
 
-def test_standalone_program_under_sanitizers(tmp_path):
+@pytest.fixture(scope="module")
+def standalone(tmp_path_factory):
     """The header alone, in a program with its own main, built with the address and undefined-
-    behaviour sanitizers: the same cases (group_cap cut to what each needs, so every array has its
-    exact size), the same answers, no report."""
+    behaviour sanitizers, run once over the cases (group_cap cut to what each needs, so every array
+    has its exact size): (todo, the plan line of each, the layout lines of those that fit)."""
     if shutil.which("g++") is None:
         pytest.skip("g++ not available")
+    tmp_path = tmp_path_factory.mktemp("plan")
     src = tmp_path / "plan_main.cpp"
     src.write_text(MAIN % HDR)
     exe = tmp_path / "plan_main"
@@ -169,6 +210,12 @@ def test_standalone_program_under_sanitizers(tmp_path):
     assert r.returncode == 0, r.stderr[-2000:]
     assert r.stderr == ""
     out = r.stdout.strip().split("\n")
+    return todo, [x for x in out if not x.startswith("L")], [x for x in out if x.startswith("L")]
+
+
+def test_standalone_program_under_sanitizers(standalone):
+    """The same cases, the same answers, no report."""
+    todo, out, _ = standalone
     assert len(out) == len(todo)
     for (in_block, pending, counts, cap, fits), line in zip(todo, out):
         v = np.array(line.split(), np.int64)
@@ -188,3 +235,39 @@ def test_standalone_program_under_sanitizers(tmp_path):
         np.testing.assert_array_equal(order, m_order)
         np.testing.assert_array_equal(gt, m_gt)
         np.testing.assert_array_equal(gf, m_first)
+
+
+def test_layouts_under_sanitizers(standalone):
+    """chunk_stage_layout and chunk_row_layout for every planned case and both units: equal to the
+    numpy models, and the properties the assembly kernel and the gate rely on, on their own."""
+    todo, _, lines = standalone
+    fitting = [t for t in todo if t[4]]
+    assert len(lines) == len(UNITS) * len(fitting)
+    for k, (in_block, pending, counts, cap, _) in enumerate(fitting):
+        n = len(pending)
+        p, c = np.asarray(pending, np.int64), np.asarray(counts, np.int64)
+        _, _, _, m_gt, m_first = model(in_block, pending, counts)
+        ng = len(m_gt)
+        for u, unit in enumerate(UNITS):
+            word = lines[len(UNITS) * k + u].split()
+            v = np.array(word[1:], np.int64)
+            assert word[0] == "L" and v[0] == unit and len(v) == 2 + n + 1 + ng
+            total, src_at, asm_total, base = int(v[1]), v[2:2 + n], int(v[2 + n]), v[3 + n:]
+            m_src, m_total = stage_model(unit, pending, counts)
+            np.testing.assert_array_equal(src_at, m_src)
+            assert total == m_total
+            m_base, m_asm = row_model(unit, in_block, m_gt, m_first)
+            np.testing.assert_array_equal(base, m_base)
+            assert asm_total == m_asm
+            # the staged chunks: in phase with the samples they follow, in call order, not overlapping
+            full = np.flatnonzero(c)
+            assert (src_at[c == 0] == 0).all()
+            assert (src_at[full] % unit == p[full] % unit).all()
+            assert (src_at[full][1:] >= (src_at[full] + c[full])[:-1]).all() and (src_at[full] >= 0).all()
+            assert total == (src_at[full[-1]] + c[full[-1]] if len(full) else 0)
+            assert total <= c.sum() + 2 * unit * n
+            # the tick rows: every group aligned, the groups not overlapping, the total their end
+            size = np.diff(m_first) * m_gt * in_block
+            assert (base % unit == 0).all() and (base >= 0).all()
+            assert (base[1:] >= (base + size)[:-1]).all()
+            assert asm_total == (base[-1] + size[-1] if ng else 0)
