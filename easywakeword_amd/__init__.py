@@ -8,10 +8,11 @@ MFCC + cosine matcher, as hand-written HIP kernels behind a C ABI
     from easywakeword_amd import WakeWord, WakeWordSet, WordMatcher, StreamEngine
 """
 from .engine import DetectorProfile, Engine, StreamEngine
+from .snapshot import StreamSnapshot
 from .wakeword import SoundBuffer, WakeWord, WakeWordSet, WordMatcher, detector_profile
 from .audio import ArraySource, WavSource, load_wav, write_wav
 from .devices import AudioDeviceManager
 
-__all__ = ["WakeWord", "WakeWordSet", "WordMatcher", "SoundBuffer", "Engine", "StreamEngine", "DetectorProfile", "detector_profile",
+__all__ = ["WakeWord", "WakeWordSet", "WordMatcher", "SoundBuffer", "Engine", "StreamEngine", "StreamSnapshot", "DetectorProfile", "detector_profile",
            "ArraySource", "WavSource", "load_wav", "write_wav", "AudioDeviceManager"]
 __version__ = "0.1.0"

@@ -48,6 +48,10 @@ EWK_PROFILE_MAX = 65536
 EWK_LISTENERS_MAX = 16       # listeners (detector profile, word) per stream
 EWK_EV_LISTENER_SHIFT = 16   # bits 16..19 of an event's flags: the listener that cut it
 EWK_CHUNK_MAX_TICKS = 64     # a chunk holds at most this many input blocks (ewk_push_chunks)
+EWK_SNAPSHOT_MAGIC = 0x4E534B45   # "EKSN": a stream snapshot (ewk_export_streams)
+EWK_SNAPSHOT_VERSION = 1
+EWK_SNAP_SECTIONS = 8
+SNAP_SECTION_NAMES = ("gate", "listeners", "block_rms", "sorted", "ring", "history", "fresh", "carry")
 
 # Every symbol include/ewk.h declares (checked by tests/test_capi.py).
 EXPORTS = [
@@ -70,6 +74,7 @@ EXPORTS = [
     "ewk_detector_profile_get", "ewk_stream_profile_assign", "ewk_stream_profiles",
     "ewk_stream_listeners_set", "ewk_stream_listeners", "ewk_get_listener_state",
     "ewk_push_chunks", "ewk_push_chunks_pcm16", "ewk_stream_pending", "ewk_chunk_plan",
+    "ewk_snapshot_plan", "ewk_snapshot_info", "ewk_export_streams", "ewk_import_streams",
 ]
 
 
@@ -97,6 +102,36 @@ class EwkDetectorProfile(C.Structure):
 class EwkListener(C.Structure):
     """ewk_listener: a stream's listener, (detector profile or -1, word of the stream bank)."""
     _fields_ = [("profile", C.c_int32), ("word", C.c_int32)]
+
+
+class EwkSnapshotSection(C.Structure):
+    _fields_ = [("offset", C.c_int64), ("bytes", C.c_int64)]
+
+
+class EwkSnapshotLayout(C.Structure):
+    """ewk_snapshot_layout: the record layout of a stream snapshot and the geometry it follows from (208 bytes)."""
+    _fields_ = [
+        ("magic", C.c_uint32), ("version", C.c_int32), ("sample_rate", C.c_int32), ("block", C.c_int32),
+        ("buffer_seconds", C.c_int32), ("ring_format", C.c_int32), ("n_blocks", C.c_int32), ("in_rate", C.c_int32),
+        ("in_block", C.c_int32), ("hist_len", C.c_int32), ("ring_len", C.c_int64), ("sring_len", C.c_int64),
+        ("tick_seconds", C.c_double), ("section", EwkSnapshotSection * EWK_SNAP_SECTIONS),
+        ("record_bytes", C.c_int64), ("fingerprint", C.c_uint64),
+    ]
+
+
+class EwkStreamMeta(C.Structure):
+    """ewk_stream_meta: the host part of one exported stream (176 bytes)."""
+    _fields_ = [
+        ("magic", C.c_uint32), ("version", C.c_int32), ("tick", C.c_int64), ("record_bytes", C.c_int64),
+        ("fingerprint", C.c_uint64), ("pending", C.c_int32), ("profile", C.c_int32), ("word", C.c_int32),
+        ("n_listeners", C.c_int32), ("listeners", EwkListener * EWK_LISTENERS_MAX),
+    ]
+
+
+STREAM_META_DTYPE = np.dtype([("magic", "<u4"), ("version", "<i4"), ("tick", "<i8"), ("record_bytes", "<i8"),
+                              ("fingerprint", "<u8"), ("pending", "<i4"), ("profile", "<i4"), ("word", "<i4"),
+                              ("n_listeners", "<i4"), ("listeners", "<i4", (EWK_LISTENERS_MAX, 2))])
+assert STREAM_META_DTYPE.itemsize == C.sizeof(EwkStreamMeta)
 
 
 PROFILE_FIELDS = tuple(f for f, _ in EwkDetectorProfile._fields_)
@@ -244,6 +279,10 @@ def load():
             "ewk_stream_pending": (C.c_int, [_P, _i32p, C.c_int32, _i32p]),
             "ewk_chunk_plan": (C.c_int, [C.c_int32, C.c_int32, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p,
                                          C.c_int32, _i32p]),
+            "ewk_snapshot_plan": (C.c_int, [C.POINTER(EwkConfig), C.c_int32, C.POINTER(EwkSnapshotLayout)]),
+            "ewk_snapshot_info": (C.c_int, [_P, C.POINTER(EwkSnapshotLayout)]),
+            "ewk_export_streams": (C.c_int, [_P, _i32p, C.c_int32, _P, _P, C.c_int64, C.c_int32]),
+            "ewk_import_streams": (C.c_int, [_P, _i32p, C.c_int32, _P, _P, C.c_int64, C.c_int32]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)

@@ -376,7 +376,7 @@ int ewk_profile_enable(ewk_engine* e, int32_t on) {
 
 int ewk_profile_read(ewk_engine* e, int32_t kind, double* total_ms, int64_t* launches) {
     if (!e || !total_ms || !launches) return fail(EWK_EINVAL, "NULL argument");
-    if (kind < 0 || kind > 4) return fail(EWK_EINVAL, "kind must be 0, 1, 2, 3 or 4");
+    if (kind < 0 || kind > 5) return fail(EWK_EINVAL, "kind must be 0, 1, 2, 3, 4 or 5");
     HIP_TRY(hipSetDevice(e->device));
     double tot = 0.0;
     for (auto& p : e->ev[kind]) {

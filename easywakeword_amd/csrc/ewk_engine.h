@@ -13,6 +13,7 @@
 #include "ewk_chunk_plan.h"
 #include "ewk_gate.h"
 #include "ewk_internal.h"
+#include "ewk_snapshot.h"
 
 namespace ewk {
 
@@ -292,7 +293,15 @@ struct ewk_engine {
 
     // measurement: (start, stop) event pairs per kernel family
     bool prof = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[5];
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[6];
+
+    // Stream snapshots (ewk_export_streams / ewk_import_streams, ewk_engine_snapshot.cpp); nothing
+    // is allocated before the first call with a host payload.  snap_dev: records between the
+    // pack / unpack launch and the DMA, two halves of snap_half bytes; snap_pin: the pinned side
+    // of each half (the DMA never touches d_ring).
+    ewk::DevBuf<unsigned char> snap_dev;
+    ewk::PinnedStage snap_pin[2];
+    size_t snap_half = 0;
     std::vector<hipEvent_t> ev_pool;
 };
 

@@ -16,6 +16,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import N_MFCC, check
+from .snapshot import StreamSnapshot, layout_dict
 
 FREQUENCY = 16000
 
@@ -122,7 +123,8 @@ class Engine:
 
     def profile_read(self, kind: int = 0):
         """(total_ms, launches) of the kernel family since the last read
-        (0 = fp32 scorer, 1 = fp64 re-scorer, 2 = gate, 3 = resampler)."""
+        (0 = fp32 scorer, 1 = fp64 re-scorer, 2 = gate, 3 = resampler, 4 = chunk assembly,
+        5 = snapshot pack / unpack)."""
         ms = C.c_double(0.0)
         n = C.c_int64(0)
         check(self._lib.ewk_profile_read(self._h, int(kind), C.byref(ms), C.byref(n)))
@@ -720,6 +722,90 @@ class StreamEngine(Engine):
         st = _lib.EwkStreamState()
         check(self._lib.ewk_get_listener_state(self._h, int(stream), int(listener), C.byref(st)))
         return {f: getattr(st, f) for f, _ in st._fields_}
+
+    # -- stream snapshots: listed streams leave this engine and continue in another ---
+    def snapshot_layout(self) -> dict:
+        """This engine's record layout at its current input rate (snapshot.layout_dict): the
+        geometry, "sections" (name -> (offset, bytes)), record_bytes and the fingerprint an
+        importer compares."""
+        l = _lib.EwkSnapshotLayout()
+        check(self._lib.ewk_snapshot_info(self._h, C.byref(l)))
+        return layout_dict(l)
+
+    def export_streams(self, streams) -> StreamSnapshot:
+        """The listed streams as a StreamSnapshot in host memory: ring, block RMSs and threshold
+        history, detector state of every listener, resampler history, pending packet samples, and
+        in `meta` the tick, profile, word and listeners.  Joins the scoring of the pushes so far
+        (their events stay here, for poll()); the streams themselves are left as they are."""
+        s = self._stream_list(streams)
+        layout = self.snapshot_layout()
+        meta = np.zeros(s.size, dtype=_lib.STREAM_META_DTYPE)
+        payload = np.zeros((s.size, layout["record_bytes"]), dtype=np.uint8)
+        check(self._lib.ewk_export_streams(self._h, _lib.i32ptr(s), s.size, meta.ctypes.data_as(C.c_void_p),
+                                           payload.ctypes.data_as(C.c_void_p), payload.nbytes, 0))
+        return StreamSnapshot(meta, payload, layout)
+
+    def import_streams(self, streams, snap: StreamSnapshot) -> None:
+        """Stream streams[i] becomes the stream of record i of `snap` and goes on producing the
+        events its source would have produced.  This engine must have the snapshot's geometry
+        (block, rings, ring format, tick, input rate) and the tables its records point into
+        (detector profiles, stream bank) set first; timings and thresholds may differ.  ValueError,
+        with nothing changed, names the record and what it does not fit."""
+        s = self._stream_list(streams)
+        if len(snap) != s.size:
+            raise ValueError(f"{len(snap)} records for {s.size} streams")
+        meta = np.ascontiguousarray(snap.meta, dtype=_lib.STREAM_META_DTYPE)
+        payload = np.ascontiguousarray(snap.payload, dtype=np.uint8)
+        check(self._lib.ewk_import_streams(self._h, _lib.i32ptr(s), s.size, meta.ctypes.data_as(C.c_void_p),
+                                           payload.ctypes.data_as(C.c_void_p), payload.nbytes, 0))
+
+    def export_streams_device(self, streams, ptr: int, cap: int) -> np.ndarray:
+        """export_streams with the records left in device memory at `ptr` (16-byte aligned, room
+        for `cap` bytes): stream-ordered on the engine's stream, no wait.  Returns the meta array."""
+        s = self._stream_list(streams)
+        meta = np.zeros(s.size, dtype=_lib.STREAM_META_DTYPE)
+        check(self._lib.ewk_export_streams(self._h, _lib.i32ptr(s), s.size, meta.ctypes.data_as(C.c_void_p),
+                                           C.c_void_p(ptr or None), int(cap), _lib.EWK_OUT_DEVICE))
+        return meta
+
+    def import_streams_device(self, streams, meta, ptr: int, nbytes: int) -> None:
+        """import_streams from records in device memory (on this engine's GPU) at `ptr`: no host
+        synchronisation; the records must stay valid until the engine's stream has passed the call."""
+        s = self._stream_list(streams)
+        m = np.ascontiguousarray(meta, dtype=_lib.STREAM_META_DTYPE).reshape(-1)
+        if m.size != s.size:
+            raise ValueError(f"{m.size} records for {s.size} streams")
+        check(self._lib.ewk_import_streams(self._h, _lib.i32ptr(s), s.size, m.ctypes.data_as(C.c_void_p),
+                                           C.c_void_p(ptr or None), int(nbytes), _lib.EWK_PCM_DEVICE))
+
+    def move_streams(self, dst_engine: "StreamEngine", src_streams, dst_streams) -> np.ndarray:
+        """Stream src_streams[i] of this engine continues as stream dst_streams[i] of `dst_engine`
+        on the same GPU, without a host copy: exported into a device buffer (a torch tensor),
+        imported from it behind an event on this engine's stream.  The source streams are left as
+        they are (reset_streams frees their slots).  Returns the meta array.  For engines on two
+        GPUs copy the records peer to peer between export_streams_device and
+        import_streams_device (INTEGRATION.md)."""
+        import torch
+        if dst_engine.gpu != self.gpu:
+            raise ValueError(f"move_streams works on one GPU (this engine: {self.gpu}, the other: {dst_engine.gpu}); "
+                             "across GPUs copy the records peer to peer (INTEGRATION.md)")
+        s = self._stream_list(src_streams)
+        d = dst_engine._stream_list(dst_streams)
+        if d.size != s.size:
+            raise ValueError(f"{s.size} source streams for {d.size} destination streams")
+        nbytes = int(s.size) * int(self.snapshot_layout()["record_bytes"])
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=torch.device("cuda", self.gpu))
+        meta = self.export_streams_device(s, buf.data_ptr(), nbytes)
+        # the import runs on the other engine's stream: behind this engine's export
+        done = torch.cuda.Event()
+        src_stream = torch.cuda.ExternalStream(self.stream_handle(), device=torch.device("cuda", self.gpu))
+        dst_stream = torch.cuda.ExternalStream(dst_engine.stream_handle(), device=torch.device("cuda", self.gpu))
+        done.record(src_stream)
+        dst_stream.wait_event(done)
+        dst_engine.import_streams_device(d, meta, buf.data_ptr(), nbytes)
+        # the buffer goes back to torch's allocator when the import has read it
+        buf.record_stream(dst_stream)
+        return meta
 
     # -- stream bank: gated events against many references, per stream ------------
     def set_stream_bank(self, stream_word=None) -> None:

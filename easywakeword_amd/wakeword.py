@@ -239,6 +239,17 @@ class SoundBuffer:
             return np.array([])
         return self.engine.read_last(0, n_samples).astype(np.float64)
 
+    def snapshot(self):
+        """Everything this buffer has heard, as a StreamSnapshot of its one stream: the ring, the
+        adaptive threshold's history, the detector state, the resampler and packet state."""
+        return self.engine.export_streams([0])
+
+    def restore(self, snap) -> None:
+        """Continue the buffer `snap` was taken from (same seconds, block and source rate): full
+        at once if that one was, with its threshold and detector state."""
+        self.engine.import_streams([0], snap)
+        self._chunked = self._chunked or bool(self.engine.stream_pending([0])[0])
+
 
 def _default_source(device):
     """The microphone `device` names (None, index, name pattern, "default"/"best"/"first"),
@@ -650,6 +661,17 @@ class WakeWord:
     def is_listening(self) -> bool:
         return self._listening
 
+    def snapshot(self):
+        """SoundBuffer.snapshot() of this detector's buffer (created on first use, as waitforit does)."""
+        self._initialize_audio()
+        return self._sound_buffer.snapshot()
+
+    def restore(self, snap) -> None:
+        """Continue from a snapshot() taken before a restart: is_buffer_full() is true at once when
+        it was there, and waitforit() detects from its first tick instead of pumping ten seconds."""
+        self._initialize_audio()
+        self._sound_buffer.restore(snap)
+
     def __del__(self):
         try:
             self.stop()
@@ -836,6 +858,16 @@ class WakeWordSet:
 
     def is_listening(self) -> bool:
         return self._listening
+
+    def snapshot(self):
+        """As WakeWord.snapshot(): the shared buffer with the detector state of every word."""
+        self._initialize_audio()
+        return self._sound_buffer.snapshot()
+
+    def restore(self, snap) -> None:
+        """As WakeWord.restore(), for a set of the same words in the same order."""
+        self._initialize_audio()
+        self._sound_buffer.restore(snap)
 
     def __del__(self):
         try:

@@ -595,6 +595,110 @@ int ewk_set_input_rate(ewk_engine* e, int32_t in_rate);
  * any pointer may be NULL. */
 int ewk_input_rate_info(ewk_engine* e, int32_t* in_rate, int32_t* in_block, int32_t* delay);
 
+/* ---- stream snapshots: export and import listed streams between engines ---------- */
+/* A stream leaves the engine it was created in and continues in any slot of another engine of the
+ * same geometry -- after a restart, on another GPU, in a rebalanced shard -- as if nothing had
+ * happened: exported after k ticks and imported elsewhere, it goes on producing the events the
+ * source would have produced, every field (ring_start included) and the score's bits.
+ *
+ * A snapshot of n streams is (a) ewk_stream_meta meta[n], always host memory: what the engine's
+ * host mirrors hold of the stream, and what an importer checks before it touches anything; and
+ * (b) a payload of n records of record_bytes each, host or device memory, stream i at payload +
+ * i * record_bytes.  A record is the stream's device state in the sections below, each starting
+ * at a multiple of 16 bytes, record_bytes a multiple of 128:
+ *   EWK_SNAP_GATE       the gate state (SoundBuffer fields and listener 0's _detect_word locals)
+ *   EWK_SNAP_LISTENERS  the _detect_word locals of listeners 1..EWK_LISTENERS_MAX-1 (40 bytes each)
+ *   EWK_SNAP_BLOCK_RMS  n_blocks float64 block RMSs
+ *   EWK_SNAP_SORTED     the same ascending (the current copy behind the adaptive threshold)
+ *   EWK_SNAP_RING       the sample ring as stored (sring_len samples of the ring's type, unrotated:
+ *                       pointer, and every later event's ring_start, stay valid)
+ *   EWK_SNAP_HISTORY    with an input rate set: the resampler's last hist_len input samples (float32)
+ *   EWK_SNAP_FRESH      ... and its flag "no push since the history was cleared" (int32)
+ *   EWK_SNAP_CARRY      the unfinished block of packet ingest: in_block samples of the ring's type,
+ *                       the first `pending` of them meaningful
+ * Every byte not covered by live state is zero (padding, listener rows past the count, the carry
+ * past `pending`, RMS rows that are not valid yet): two exports of an untouched stream are
+ * byte-identical, and a record exported straight after an import equals the imported one.
+ *
+ * The layout is a function of the geometry alone: sample_rate, block, buffer_seconds / ring_len,
+ * sring_len, ring_format, n_blocks, tick_seconds, and the input rate with its in_block and
+ * hist_len.  Its fingerprint is a 64-bit hash of exactly those.  Gate durations, thresholds and
+ * similarity_threshold are not geometry: a stream may be imported into an engine with other
+ * timings, exactly as a profile assignment changes them under a running stream.
+ *
+ * Queued events are not part of a snapshot: they stay in the source's banks for ewk_poll. */
+#define EWK_SNAPSHOT_MAGIC 0x4e534b45u   /* "EKSN" */
+#define EWK_SNAPSHOT_VERSION 1
+#define EWK_SNAP_GATE 0
+#define EWK_SNAP_LISTENERS 1
+#define EWK_SNAP_BLOCK_RMS 2
+#define EWK_SNAP_SORTED 3
+#define EWK_SNAP_RING 4
+#define EWK_SNAP_HISTORY 5
+#define EWK_SNAP_FRESH 6
+#define EWK_SNAP_CARRY 7
+#define EWK_SNAP_SECTIONS 8
+typedef struct ewk_snapshot_section { int64_t offset; int64_t bytes; } ewk_snapshot_section;
+typedef struct ewk_snapshot_layout {   /* 208 bytes */
+    uint32_t magic;               /* EWK_SNAPSHOT_MAGIC */
+    int32_t version;              /* EWK_SNAPSHOT_VERSION */
+    int32_t sample_rate, block, buffer_seconds, ring_format, n_blocks;
+    int32_t in_rate;              /* the rate pushes arrive at (sample_rate without a resampler) */
+    int32_t in_block;             /* samples per tick at in_rate */
+    int32_t hist_len;             /* resampler history samples per stream (0 without a resampler) */
+    int64_t ring_len, sring_len;
+    double tick_seconds;
+    ewk_snapshot_section section[EWK_SNAP_SECTIONS];
+    int64_t record_bytes;
+    uint64_t fingerprint;
+} ewk_snapshot_layout;
+typedef struct ewk_stream_meta {       /* 176 bytes */
+    uint32_t magic;
+    int32_t version;
+    int64_t tick;                 /* ticks delivered to the stream (ewk_stream_ticks) */
+    int64_t record_bytes;         /* of the layout the record was written with */
+    uint64_t fingerprint;         /* ... and its geometry */
+    int32_t pending;              /* samples in the carry (ewk_stream_pending) */
+    int32_t profile;              /* detector profile of listener 0 (-1: the engine's configuration) */
+    int32_t word;                 /* stream-bank word of listener 0 (0 without a stream bank) */
+    int32_t n_listeners;          /* 1..EWK_LISTENERS_MAX */
+    ewk_listener listeners[EWK_LISTENERS_MAX];   /* rows 0..n_listeners-1 (row 0 = profile, word); the rest {-1, 0} */
+} ewk_stream_meta;
+
+/* The layout of a configuration (NULL: the defaults) at an input rate (0 or sample_rate: none).
+ * Host only: no engine, no device.  EWK_EINVAL, with nothing written, for a configuration
+ * ewk_create would refuse or a rate ewk_set_input_rate would refuse for it. */
+int ewk_snapshot_plan(const ewk_config* cfg, int32_t in_rate, ewk_snapshot_layout* out);
+/* The engine's own layout, with its current input rate.  EWK_EINVAL for an engine without streams. */
+int ewk_snapshot_info(ewk_engine* e, ewk_snapshot_layout* out);
+/* Export: meta[i] and record i describe stream streams[i] (`streams` as for ewk_push_streams).
+ * payload is host memory, or device memory with EWK_OUT_DEVICE; EWK_EINVAL, with nothing written,
+ * when cap_bytes < n * record_bytes.  Waits for nothing but joins the scoring of the pushes so
+ * far on the engine's stream first, so their events are scored and queued in this engine.  The
+ * exported streams are left as they are: export is a read.  To device memory the call is
+ * stream-ordered on the engine's stream, without host synchronisation; to host memory it returns
+ * when the payload is in the caller's buffer (copied through bounded pinned staging, two buffers
+ * of at most 32 MB or one record).  meta comes from the host mirrors alone. */
+int ewk_export_streams(ewk_engine* e, const int32_t* streams, int32_t n, ewk_stream_meta* meta,
+                       void* payload, int64_t cap_bytes, int32_t flags);
+/* Import: stream streams[i] of e becomes the stream of record i.  payload is host memory, or
+ * device memory with EWK_PCM_DEVICE (then no host synchronisation is made; the payload must stay
+ * valid until the engine's stream has passed the call).  Everything is checked on the host before
+ * anything is enqueued, and a refused import (EWK_EINVAL) changes nothing, on the device or in a
+ * host mirror: the list; bytes == n * record_bytes; every meta's magic, version, record_bytes and
+ * fingerprint against the engine's own layout (the input rate in force included); pending in [0,
+ * in_block); every listener row as ewk_stream_listeners_set checks it -- profile in [-1,
+ * n_profiles), word in [0, n_words) with the stream bank on and 0 with it off -- with a message
+ * naming the stream and the table.  The caller sets the tables first; it may reassign afterwards
+ * with the assign calls, which keep the FSM state and the clock.
+ * The import desynchronises the engine (as a subset push does), sets each stream's tick, pending
+ * count, profile, word and listeners, allocating what the first such call allocates, and scatters
+ * the records on the engine's stream.  The ring row is written with agent-scope stores, as every
+ * ring initialisation is.  Events of a slot's previous occupant that are still queued stay
+ * queued, as after ewk_reset_stream_list. */
+int ewk_import_streams(ewk_engine* e, const int32_t* streams, int32_t n, const ewk_stream_meta* meta,
+                       const void* payload, int64_t bytes, int32_t flags);
+
 /* ---- measurement ------------------------------------------------------------ */
 /* When enabled, these launches are bracketed by hipEvents on the stream they run on:
  * the scorer and re-score launches of ewk_score_segments_device, of the bank scoring
@@ -605,7 +709,8 @@ int ewk_input_rate_info(ewk_engine* e, int32_t* in_rate, int32_t* in_block, int3
  * the summed device time and launch count per kernel family, then clears.
  * kind: 0 = fp32 MFCC scorer (k_score_f32), 1 = fp64 re-scorer, 2 = gate ticks,
  * 3 = resampler launches (ewk_resample, and the resample + history save of a push),
- * 4 = the assembly launch of a chunk push (ewk_push_chunks*). */
+ * 4 = the assembly launch of a chunk push (ewk_push_chunks*),
+ * 5 = the pack and unpack launches of ewk_export_streams / ewk_import_streams. */
 int ewk_profile_enable(ewk_engine* e, int32_t on);
 int ewk_profile_read(ewk_engine* e, int32_t kind, double* total_ms, int64_t* launches);
 
