@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import synth
+import template_cases
 from golden_io import matcher_fixture, score_close, template_arrays
 from oracle import mfcc_ref
 
@@ -38,6 +39,11 @@ def test_template_from_wav_matches_reference(engine, fixture):
     tm, ts = template_arrays(fx)
     np.testing.assert_allclose(m, tm, rtol=1e-4, atol=2e-3)
     np.testing.assert_allclose(s, ts, rtol=1e-4, atol=2e-3)
+    # the tolerances above let through errors that move scores by several 1e-4 (a 1e-3 error per
+    # coefficient: 2.5e-4, tests/test_template_cases.py); the bar itself, in score units:
+    drift = template_cases.template_drift((m, s), (tm, ts), template_cases.candidate_stats())
+    print("template drift vs the reference's template =", drift)
+    assert drift <= SCORE_TOL
 
 
 @pytest.mark.parametrize("ref_dtype", ["float64", "float32"])
