@@ -77,7 +77,8 @@
 #define EWK_PASS_ARG(x)
 #endif
 #ifdef EWK_TIMING
-constexpr int kDbgN = 24;   // [20] masked tiles, [21] cycles of their DCT + mask DCT + sums, [22] [23] cycles and count of the plain tile DCTs
+constexpr int kDbgN = 27;   // [20] masked tiles, [21] cycles of their DCT + mask DCT + sums, [22] [23] cycles and count of the plain tile DCTs,
+                            // [24] tiles with clamped entries left without a mask (mask_wanted), [25] [26] those recomputed later: tiles, passes
 #endif
 
 namespace ewk {
@@ -1317,7 +1318,9 @@ __device__ __forceinline__ void work_describe(const WorkCtx& c, WorkAhead& w) {
 // (bench batch: 16 % of the tiles recomputed in time order, ~5 % in scout order).  When the
 // clamp rises, the clamped entries of the earlier tiles move up with it inside the sums
 // (ewk_topdb_shift.h); only the passes of a tile that hold an unclamped value below the final
-// threshold are recomputed (0.06 per bench segment).
+// threshold are recomputed (0.06 per bench segment).  A tile joins those sums (its mask DCT) only
+// while the scout still ranks a tile to come near the loudest (mask_wanted: 1.25 of the 2.99
+// tiles with clamped entries per bench segment); the others are recomputed if the clamp does rise.
 template <int RING>
 __device__ void segment_stats(const SegSrc<RING>& v, const unsigned char* smem, float* scr, float* tile,
                               float* spec, int lane, const int (&lo)[8], double (&s1)[kSlots], double (&s2)[kSlots],
@@ -1330,9 +1333,15 @@ __device__ void segment_stats(const SegSrc<RING>& v, const unsigned char* smem, 
     const int col = lane & 15;
     int* order = reinterpret_cast<int*>(spec + kSpecOrder);
     const bool ordered = ntile > 1 && ntile <= kSpecTiles;
+    // the tiles that may get a mask: positions 0 .. near - 2 (mask_wanted); a segment taken in
+    // time order keeps every mask, a single tile is its own last
+    int near = ntile > 1 ? kSpecTiles + 1 : 1;
     if (ordered) {   // loudest-first order: lane t ranks tile t (ties by index)
         float e = scout_tiles(v, ntile, lane);
         e = e == e ? e : 0.0f;   // NaN samples: a total order (unique ranks) all the same
+        // (lanes past ntile hold -1: never the max, never near)
+        const float e_max = wave_max(e);
+        near = __builtin_popcountll(__ballot(lane < ntile && mask_near(e, e_max)));
         int rank = 0;
         for (int u = 0; u < ntile; ++u) {
             const float eu = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e), u));
@@ -1367,6 +1376,9 @@ __device__ void segment_stats(const SegSrc<RING>& v, const unsigned char* smem, 
 #pragma unroll
     for (int i = 0; i < kSlots; ++i) { sA[i] = 0.0f; sB[i] = 0.0f; sC[i] = 0.0f; }
     uint64_t shifted = 0;
+#ifdef EWK_TIMING
+    uint64_t skipped = 0;   // tiles with clamped entries left without a mask
+#endif
     for (int k = 0; k < ntile; ++k) {
         EWK_TS(tk0);
         const int next_tile = k + 1 < ntile ? (ordered ? order[k + 1] : k + 1) : -1;
@@ -1410,8 +1422,21 @@ __device__ void segment_stats(const SegSrc<RING>& v, const unsigned char* smem, 
             srun = run;
         }
         // a tile with clamped entries (only such a tile can be wrong once the max rises again):
-        // its mask DCT joins the shift sums and its record is the minimum above the clamp
-        const bool masked = rec && tmw < run;
+        // its mask DCT joins the shift sums and its record is the minimum above the clamp.
+        // Only where the clamp can still rise (mask_wanted, ewk_topdb_shift.h: a tile near the
+        // loudest by the scout is still to come; never the last tile, whose clamp is theta).
+        // Left without a mask the tile is kept like one without clamped entries: records
+        // fmaxf(pass min, run) (== run for a pass that holds a clamped entry), amin the same,
+        // shifted bit 0, nothing in A / B / C.  If no later tile raises the clamp nothing differs,
+        // bit for bit; if one does, those passes have record == run < theta, shift_flags selects
+        // them and fix_tile(shifted = false) rebuilds the stored columns at the tile's recorded
+        // run (spec[kSpecRun]: for a self-clamped tile the run after its own rise, as for a masked
+        // one) and swaps them with stats_replace.  shift_apply only moves tiles that joined the sums.
+        const bool clamped = rec && tmw < run;
+        const bool masked = clamped && mask_wanted(k, near);
+#ifdef EWK_TIMING
+        if (clamped && !masked) { dbg[24] += 1; skipped |= 1ull << tile_i; }
+#endif
         const bool ok = tile_i * 16 + col < T;
         float c[kSlots], m[kSlots], mnab = INFINITY;
         EWK_TS(tm0);
@@ -1474,6 +1499,7 @@ __device__ void segment_stats(const SegSrc<RING>& v, const unsigned char* smem, 
 #ifdef EWK_TIMING
             dbg[10] += 1;
             dbg[11] += __builtin_popcount(mask);
+            if (rec && ((skipped >> cur) & 1)) { dbg[25] += 1; dbg[26] += __builtin_popcount(mask); }
 #endif
             fix_tile(v, cur, T, rec ? spec[kSpecRun + cur] : -INFINITY, theta, smem, scr, tile, lane, lo, cref, s1,
                      s2, mask, rec && ((shifted >> cur) & 1));

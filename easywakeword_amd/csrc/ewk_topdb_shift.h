@@ -43,6 +43,22 @@ EWK_SHIFT_HD void shift_rise(double delta, TA A, TB& B, TA C, double& s1, double
 template <typename T>
 EWK_SHIFT_HD bool shift_flags(T min_above_clamp, T theta) { return min_above_clamp < theta; }
 
+// Which tiles get a mask at all.  A tile's mask is used only if a tile processed after it raises
+// the clamp.  The tiles are processed in descending scout energy e, so the loudest tile still to
+// come is the next one: the tile at position k gets a mask only if tile k + 1 is "near" the
+// loudest by the scout (e >= ratio e_max; NaN already mapped to 0), that is if k + 1 < K with K
+// the number of near tiles.  The last tile never needs one (theta equals its clamp).  A zero or
+// all-equal scout makes every tile near: all but the last are masked.  Only a cost heuristic: a
+// tile left without a mask is stored and recorded like a tile without clamped entries -- the
+// record of a pass that holds one is the clamp itself -- so a later rise flags exactly those
+// passes (shift_flags) and they are recomputed and swapped as plain columns, which never joined
+// A, B, C.
+#ifndef EWK_MASK_NEAR_RATIO
+#define EWK_MASK_NEAR_RATIO 0.1f   // 10^(-X / 10), X = 10 dB (profiles/r08_v1_scout_sim_mask_rule.txt)
+#endif
+EWK_SHIFT_HD bool mask_near(float e, float e_max, float ratio = EWK_MASK_NEAR_RATIO) { return e >= ratio * e_max; }
+EWK_SHIFT_HD bool mask_wanted(int k, int near_tiles) { return k + 1 < near_tiles; }
+
 // A recomputed column: out goes the stored one as the rises have moved it (co + delta m,
 // delta = theta - its own clamp), in comes cn (the column clamped at theta).
 EWK_SHIFT_HD void shift_replace(double cn, double co, double m, double delta, double cref, double& s1, double& s2) {

@@ -36,7 +36,7 @@ print(f"{lib:28s} L={fixed or 'ragged'} {ms:8.3f} ms  {frames/ms/1e6:7.3f} Gfram
 import ctypes
 lib = ctypes.CDLL(os.environ.get("EWK_LIB") or os.path.join(ROOT, "easywakeword_amd", "libewk.so"))
 if hasattr(lib, "ewk_debug_timing"):   # -DEWK_TIMING builds (easywakeword_amd/libewk_timing.so)
-    buf = (ctypes.c_ulonglong * 24)()   # kDbgN (ewk_mfcc.hip)
+    buf = (ctypes.c_ulonglong * 32)()   # >= kDbgN (ewk_mfcc.hip; 24 before the mask-skip counters)
     lib.ewk_debug_timing(buf)      # reset
     e.profile(False)
     step(); torch.cuda.synchronize()
@@ -58,6 +58,10 @@ if hasattr(lib, "ewk_debug_timing"):   # -DEWK_TIMING builds (easywakeword_amd/l
               f"{buf[21] / segs:,.0f} per segment ({100.0 * buf[21] / max(1, tot):.2f}%); plain DCT {plain:,.0f} cycles per "
               f"other tile; the mask's share of it {(mphase - plain) * buf[20] / segs:,.0f} per segment "
               f"({100.0 * (mphase - plain) * buf[20] / max(1, tot):.2f}%)")
+    # masks only where the clamp can still rise (mask_wanted): the tiles with clamped entries left
+    # without one, and those of them a later rise made the fix-up recompute
+    print(f"  masks built/segment={buf[20] / segs:.3f} skipped/segment={buf[24] / segs:.3f}; skipped tiles later "
+          f"recomputed/segment={buf[25] / segs:.4f} passes/segment={buf[26] / segs:.4f}")
     if buf[19]:   # frame-pass sub-phases (first-pass passes only)
         sub = ["window+DFT16a", "twiddle", "transposes", "DFT16b", "untangle+power", "mel+log", "tile write+stage"]
         print(f"  per frame pass ({buf[19] / waves:,.0f} per wave): " +

@@ -11,6 +11,12 @@ order: a tile's clamped entries move up with the clamp inside the statistics, so
 recomputed only if one of its unclamped stored values lies between its own clamp and the final
 threshold.  They also give the share of tiles that hold a clamped entry (the tiles that pay for
 the mask DCT) and break the counts down per segment kind of the bench recipe.
+
+    python scripts/scout_sim.py mask [n]
+replays "masks only where the clamp can still rise" (mask_near / mask_wanted in
+csrc/ewk_topdb_shift.h) on the ragged batch (4n/3 segments), L = 16,000 and L = 6,400 (n each):
+per window X the masks built, the clamped tiles left without a mask that a later rise recomputes,
+and the recomputed passes (profiles/r08_v1_scout_sim_mask_rule.txt).
 """
 import os
 import sys
@@ -136,6 +142,101 @@ def replay_rules(L, order):
     return out
 
 
+def scout_energy(y, ntile):
+    return np.array([float((sample_rows(y, t, 4, 64, 640, 64).astype(np.float32) ** 2).sum()) for t in range(ntile)])
+
+
+def replay_mask_rule(L, order, e, X):
+    """Replay "masks only where the clamp can still rise" (mask_near / mask_wanted in
+    csrc/ewk_topdb_shift.h) over the raw log-mel L [128, T] in scout order `order` (scout
+    energies e).  X: the window in dB; None = every tile with a clamped entry is masked (the rule
+    before), inf = all but the last.  Returns masks built, clamped tiles left without one, those
+    of them recomputed later (tiles, passes), and all recomputed passes."""
+    T = L.shape[1]
+    theta = L.max() - 80.0
+    if X is None:
+        near = len(order) + 1
+    else:
+        emax = max(float(e.max()), 0.0)
+        near = int(sum(1 for t in order if e[t] >= 10.0 ** (-X / 10.0) * emax)) if np.isfinite(X) else len(order)
+    out = {"masks": 0, "skipped": 0, "skipped_fixed_tiles": 0, "skipped_fixed_passes": 0, "passes": 0,
+           "near": min(near, len(order)), "kept_shifted_passes": 0, "first_skipped_fixed": 0, "rises": 0}
+    run = -np.inf
+    for k, t in enumerate(order):
+        X16 = L[:, 16 * t:min(T, 16 * t + 16)]
+        out["rises"] += bool(k and X16.max() - 80.0 > run)
+        run = max(run, X16.max() - 80.0)
+        clamped = bool(X16.min() < run)
+        masked = clamped and k + 1 < near
+        out["masks"] += masked
+        out["skipped"] += clamped and not masked
+        fixed = 0
+        for p in (0, 8):
+            P = X16[:, p:p + 8]
+            if P.size == 0:
+                continue
+            if masked:      # record: the minimum above the clamp
+                free = P[P > run]
+                flag = bool(free.size and free.min() < theta)
+                # shifted by a decibel or more with a mask neither empty nor full, never recomputed
+                out["kept_shifted_passes"] += bool(not flag and P.min() < run and free.size and theta - run >= 1.0)
+                fixed += flag
+            else:           # record: max(pass minimum, run)
+                fixed += bool(max(P.min(), run) < theta)
+        out["passes"] += fixed
+        if clamped and not masked and fixed:
+            out["skipped_fixed_tiles"] += 1
+            out["skipped_fixed_passes"] += fixed
+            out["first_skipped_fixed"] += k == 0
+    return out
+
+
+MASK_CYCLES = 3292      # a masked tile beyond a plain DCT (profiles/r07_v3_phase_timing.txt: 5,085 - 1,793)
+PASS_CYCLES = 9500      # a recomputed pass with its share of fix_tile's two DCTs (assumed, not measured)
+
+
+def mask_rule_table(n, fixed):
+    """The table of the mask rule for one bench batch: per window X the masks built, the clamped
+    tiles left without one that a later rise recomputes, and the recomputed passes, per segment."""
+    import torch
+    import bench
+    word = bench.load_word()
+    pcm, off, ln, frames, lengths, offsets = bench.make_segments(torch, torch.device("cpu"), n, 1234, word,
+                                                                   fixed_len=fixed)
+    pcm = pcm.numpy()
+    rows = [("always (before)", None), ("X =  3 dB", 3.0), ("X =  6 dB", 6.0), ("X = 10 dB", 10.0),
+            ("X = 20 dB", 20.0), ("all but the last", np.inf)]
+    tot = {name: None for name, _ in rows}
+    followed = 0
+    for i in range(n):
+        y = pcm[offsets[i]:offsets[i] + lengths[i]].astype(np.float32)
+        L = log_mel_raw(y)
+        ntile = (L.shape[1] + 15) // 16
+        e = scout_energy(y, ntile)
+        order = sorted(range(ntile), key=lambda t: (-e[t], t))
+        for name, X in rows:
+            r = replay_mask_rule(L, order, e, X)
+            tot[name] = r if tot[name] is None else {k: tot[name][k] + r[k] for k in r}
+        # masked tiles (rule before) with any rise of the clamp after them
+        run, runs = -np.inf, []
+        for t in order:
+            X16 = L[:, 16 * t:16 * t + 16]
+            run = max(run, X16.max() - 80.0)
+            runs.append((run, bool(X16.min() < run)))
+        followed += sum(1 for r, c in runs if c and r < runs[-1][0])
+    base = tot["always (before)"]
+    print(f"mask rule, {n} segments, fixed_len={fixed or 'ragged'}: masked tiles/segment {base['masks'] / n:.3f}, "
+          f"of them followed by any rise {followed / n:.3f}")
+    print("  rule               masks/seg  skipped/seg  skipped recomputed: tiles/seg passes/seg  all passes/seg  "
+          "extra passes/seg  modelled cycles/seg")
+    for name, _ in rows:
+        r = tot[name]
+        extra = (r["passes"] - base["passes"]) / n
+        print(f"  {name:18s} {r['masks'] / n:9.3f} {r['skipped'] / n:12.3f} {r['skipped_fixed_tiles'] / n:29.4f} "
+              f"{r['skipped_fixed_passes'] / n:10.4f} {r['passes'] / n:15.4f} {extra:17.4f} "
+              f"{(r['masks'] * MASK_CYCLES + (r['passes'] - base['passes']) * PASS_CYCLES) / n:20,.0f}")
+
+
 POS = {}
 PARK = {}
 
@@ -160,6 +261,11 @@ def simulate(order, tmax, tmin, pmin, name=""):
 def main():
     import torch
     import bench
+    if len(sys.argv) > 1 and sys.argv[1] == "mask":   # the mask rule's table for the three bench batches
+        n = int(sys.argv[2]) if len(sys.argv) > 2 else 300
+        for fixed in (0, 16000, 6400):
+            mask_rule_table(n + n // 3 if fixed == 0 else n, fixed)
+        return
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 1500
     fixed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     word = bench.load_word()
