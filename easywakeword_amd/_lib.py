@@ -61,7 +61,7 @@ EXPORTS = [
     "ewk_score_segments", "ewk_score_segments_device", "ewk_score_segments_f64",
     "ewk_push", "ewk_push_many", "ewk_poll", "ewk_get_stream_state", "ewk_read_last",
     "ewk_read_segment", "ewk_reset_streams", "ewk_set_similarity_threshold",
-    "ewk_profile_enable", "ewk_profile_read",
+    "ewk_profile_enable", "ewk_profile_read", "ewk_gate_launch_info",
     "ewk_push_pcm16", "ewk_push_many_pcm16", "ewk_normalize_segments", "ewk_normalize_events",
     "ewk_decode_pcm16", "ewk_poll_lagged", "ewk_runtime_info", "ewk_reenter", "ewk_compact_positives",
     "ewk_bank_set", "ewk_bank_from_pcm", "ewk_bank_clear", "ewk_bank_info", "ewk_bank_get",
@@ -238,6 +238,7 @@ def load():
             "ewk_reenter": (C.c_int, [_P, C.c_int32, C.c_double]),
             "ewk_profile_enable": (C.c_int, [_P, C.c_int32]),
             "ewk_profile_read": (C.c_int, [_P, C.c_int32, _dp, _i64p]),
+            "ewk_gate_launch_info": (C.c_int, [_P, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p]),
             "ewk_push_pcm16": (C.c_int, [_P, _P, C.c_int64, C.c_int32]),
             "ewk_push_many_pcm16": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
             "ewk_normalize_segments": (C.c_int, [_P, _P, C.c_int64, _i64p, _i32p, C.c_int32, _P, C.c_int32]),

@@ -285,6 +285,8 @@ int ewk_create(ewk_engine** out, int device, int32_t n_streams, const ewk_config
             if ((err = hipMemcpy(e->d_trees, tr.data(), kNumTrees * sizeof(PwTree), hipMemcpyHostToDevice)) != hipSuccess)
                 return bail(err, "trees");
             e->gate_val_len = gate_val_len(tr.data(), e->n_blocks);
+            e->gate_tree_kind[0] = pw_tree_kind(tr[kTreeBlockRem]);
+            e->gate_tree_kind[1] = pw_tree_kind(tr[kTreeLastRem]);
         }
         e->ev_cap = std::max(4096, 4 * n_streams);
         if ((err = reserve_rescore(e, e->ev_cap)) != hipSuccess) return bail(err, "rescore list");
@@ -390,6 +392,19 @@ int ewk_profile_read(ewk_engine* e, int32_t kind, double* total_ms, int64_t* lau
     *total_ms = tot;
     *launches = (int64_t)e->ev[kind].size();
     e->ev[kind].clear();
+    return EWK_OK;
+}
+
+int ewk_gate_launch_info(ewk_engine* e, int32_t* rb, int32_t* dma, int32_t* prof, int32_t* lsn,
+                         int32_t* block_tree_kind, int32_t* last_tree_kind) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (e->n_streams <= 0) return fail(EWK_EINVAL, "engine has no streams");
+    if (rb) *rb = e->gate_last.rb;
+    if (dma) *dma = e->gate_last.dma;
+    if (prof) *prof = e->gate_last.prof;
+    if (lsn) *lsn = e->gate_last.lsn;
+    if (block_tree_kind) *block_tree_kind = e->gate_tree_kind[0];
+    if (last_tree_kind) *last_tree_kind = e->gate_tree_kind[1];
     return EWK_OK;
 }
 

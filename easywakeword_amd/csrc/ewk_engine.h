@@ -272,6 +272,10 @@ struct ewk_engine {
     int32_t gate_grid_cap = 0;     // EWK_GATE_GRID_MAX at ewk_create: workgroups per gate launch (0: the built-in maximum)
     int32_t gate_stage = 0;
     int32_t gate_val_len = 0;       // per-wave LDS doubles of the gate (tree values, sort scratch)
+    // ewk_gate_launch_info: the instantiation of the last gate launch (-1 before the first) and
+    // how the block and last-window sums are evaluated (pw_tree_kind of the two sub-chunk trees)
+    ewk::GateFamily gate_last = {-1, -1, -1, -1};
+    int32_t gate_tree_kind[2] = {-1, -1};
 
     // input-rate resampler (ewk_resample.hip).  rs_in: the filter of ewk_set_input_rate, with the
     // per-stream history ([n_streams][H] float32: the last H input samples) and the resampled

@@ -412,6 +412,7 @@ int ewk::gate_ticks(ewk_engine* e, const TickSrc& src, int32_t rows, int32_t n_t
             ProfScope ps(e, 2, s);
             HIP_TRY(launch_gate(g, s, e->gate_grid_cap));
         }
+        e->gate_last = gate_family(g);   // (what launch_gate dispatched on)
         if (!streams) e->tick += nt;
         else for (int32_t i = 0; i < rows; ++i) e->tick_delta[streams[i]] += nt;
         int rc = score_after_gate(e, k, s);

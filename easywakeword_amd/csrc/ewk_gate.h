@@ -124,6 +124,47 @@ struct GateArgs {
 // grid_cap > 0: at most that many workgroups (ewk_create's EWK_GATE_GRID_MAX), below the
 // compile-time maximum; a wave then takes more than one row from 4 * grid_cap rows on.
 hipError_t launch_gate(const GateArgs& g, hipStream_t s, int grid_cap = 0);
+
+// register-resident block RMS arrays up to 64 * kGateRegMax blocks (10 s ring: block >= 313 samples)
+constexpr int kGateRegMax = 8;
+constexpr int kDma4Chunks = 8;     // 16-B DMA path: ticks of up to 8 * 256 samples copied to the ring in one batch
+constexpr int kPcm16Pieces = 4;    // int16 path: ticks of up to 4 * 512 samples in 16-B pieces
+
+// The k_gate_ticks<RB, DMA, PROF, LSN> instantiation a launch runs, chosen from its arguments alone
+// (ewk_gate_launch_info reports the engine's last one).
+//   rb:  2 or kGateRegMax block-RMS slots per lane in registers, 0 = the arrays stay in global memory
+//   dma: 0 = the tick through registers (sums from the stage when there is one, else from the ring),
+//        1 = LDS-DMA in 4-byte pieces, 2 = LDS-DMA in 16-byte pieces, 3 = int16 input in 16-byte
+//        pieces with an int16 stage
+//   prof / lsn: the per-stream timings / the listener lanes are compiled in
+struct GateFamily {
+    int32_t rb, dma, prof, lsn;
+};
+inline GateFamily gate_family(const GateArgs& g) {
+    GateFamily f;
+    f.lsn = g.lsn_count != nullptr;
+    f.prof = f.lsn || g.profiles != nullptr;
+    f.rb = g.n_blocks <= 128 ? 2 : g.n_blocks <= 64 * kGateRegMax ? kGateRegMax : 0;
+    // float32 input with the tick and the last window in the stage
+    const int64_t nl = g.n_last < g.ring_len ? g.n_last : g.ring_len;
+    const bool dma = g.pcm16 == nullptr && g.stage >= g.block && g.stage >= nl;
+    // 16-B pieces: every tick row 16-B aligned, whole 4-sample groups that never straddle the ring wrap
+    const bool dma4 = dma && g.block % 4 == 0 && g.block <= 256 * kDma4Chunks &&
+                      g.stride % 4 == 0 && g.tick_stride % 4 == 0 && g.ring_len % 4 == 0 && g.sring_len % 4 == 0 &&
+                      ((uintptr_t)g.pcm & 15) == 0;
+    // int16 input in 16-B pieces: rows 16-B aligned, whole 8-sample groups
+    const bool vec16 = g.pcm16 != nullptr && g.block % 8 == 0 && g.block <= 512 * kPcm16Pieces &&
+                       g.stride % 8 == 0 && g.tick_stride % 8 == 0 && g.sring_len % 8 == 0 &&
+                       ((uintptr_t)g.pcm16 & 15) == 0;
+    f.dma = f.rb == 0 ? 0 : dma4 ? 2 : vec16 ? 3 : dma ? 1 : 0;
+    return f;
+}
+// How tree_sumsq evaluates a PwTree: 0 = one leaf of fewer than 8 elements (a plain loop), 1 = one
+// leaf (8 accumulators), 2 = balanced (DPP, no LDS), 3 = the general LDS tree.
+inline int pw_tree_kind(const PwTree& t) {
+    if (t.n_leaves <= 1) return t.n < 8 ? 0 : 1;
+    return t.balanced ? 2 : 3;
+}
 // ewk_reset_stream_list: streams ids[0..n) back to the state ewk_reset_streams gives every stream,
 // in one launch: ring row zeroed with k_ring_zero's agent-scope stores, block RMS row zeroed,
 // GateStream = init, and with a resampler its history row zeroed and its fresh flag set.
@@ -168,8 +209,6 @@ hipError_t launch_listeners_set(const ListenerSetArgs& a, hipStream_t s);
 // Zero a ring with agent-scope (sc1) stores: the lines go to memory and are dropped from the
 // writing XCD's L2, so no cached copy of the initial zeros outlives the gate's first writes.
 hipError_t launch_ring_zero(void* p, size_t bytes, hipStream_t s);
-// register-resident block RMS arrays up to 64 * kGateRegMax blocks (10 s ring: block >= 313 samples)
-constexpr int kGateRegMax = 8;
 int gate_val_len(const PwTree* trees_host, int n_blocks);
 // per-wave sample staging length for a config (0 when the lengths exceed the LDS budget)
 int gate_stage_len(int block, int64_t n_last);

@@ -292,7 +292,9 @@ __device__ double pw_sumsq(const MakeSrc& make, int n, const PwTree* full, const
     double acc = 0.0;
     for (int c0 = 0; c0 < n; c0 += kPwChunk) {
         const int cn = min(kPwChunk, n - c0);
-        acc += tree_sumsq(make(c0), cn == kPwChunk ? full : rem, lane, val);   // (full->n == kPwChunk)
+        // the final (or only) chunk has its own tree, also when it is a whole chunk: n == kPwChunk
+        // has no full-chunk tree at all (ewk_create builds that one for n > kPwChunk only)
+        acc += tree_sumsq(make(c0), c0 + kPwChunk < n ? full : rem, lane, val);   // (full->n == kPwChunk)
     }
     return acc;
 }
@@ -362,9 +364,7 @@ constexpr int kGateWavesPerEU = EWK_GATE_WPE;
 #define EWK_GATE_GRID_MAX 131072
 #endif
 constexpr int kGateGridMax = EWK_GATE_GRID_MAX;
-constexpr int kDma4Chunks = 8;
-constexpr int kPcm16Pieces = 4;    // int16 path: ticks of up to 4 * 512 samples in 16-B pieces
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));     // 16-B DMA path: ticks of up to 8 * 256 samples copied to the ring in one batch
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 constexpr int kIngestLoads = 4;    // tick samples per lane loaded ahead of the ring stores (16: 166 VGPRs, 3 waves/SIMD, 10 % slower)
 
 // ---- register-resident block RMS multiset (n_blocks <= 64 * RB) ------------------
@@ -1241,6 +1241,26 @@ int gate_val_len(const PwTree* trees_host, int n_blocks) {
     return std::max(2, (m + 1) & ~1);
 }
 
+// The instantiations of one (PROF, LSN) pair: RB 2 and kGateRegMax with every DMA, and <0, 0>.
+template <bool PROF, bool LSN>
+static void launch_gate_family(const GateFamily& f, int grid, size_t lds, hipStream_t s, const GateArgs& g) {
+#define EWK_GATE_LAUNCH(RB, DMA) hipLaunchKernelGGL((k_gate_ticks<RB, DMA, PROF, LSN>), dim3(grid), dim3(256), lds, s, g)
+    if (f.rb == 2) {
+        if (f.dma == 2) EWK_GATE_LAUNCH(2, 2);
+        else if (f.dma == 3) EWK_GATE_LAUNCH(2, 3);
+        else if (f.dma == 1) EWK_GATE_LAUNCH(2, 1);
+        else EWK_GATE_LAUNCH(2, 0);
+    } else if (f.rb == kGateRegMax) {
+        if (f.dma == 2) EWK_GATE_LAUNCH(kGateRegMax, 2);
+        else if (f.dma == 3) EWK_GATE_LAUNCH(kGateRegMax, 3);
+        else if (f.dma == 1) EWK_GATE_LAUNCH(kGateRegMax, 1);
+        else EWK_GATE_LAUNCH(kGateRegMax, 0);
+    } else {
+        EWK_GATE_LAUNCH(0, 0);
+    }
+#undef EWK_GATE_LAUNCH
+}
+
 hipError_t launch_gate(const GateArgs& g, hipStream_t s, int grid_cap) {
     if (g.n_streams <= 0 || g.n_ticks <= 0) return hipSuccess;
     // one wave per stream (the hardware refills freed slots), up to kGateGridMax workgroups
@@ -1248,67 +1268,14 @@ hipError_t launch_gate(const GateArgs& g, hipStream_t s, int grid_cap) {
     const bool lsn = g.lsn_count != nullptr;
     if (lsn ? (!g.lsn_tab || !g.lsn_st || !g.stream_profile) : (g.profiles == nullptr) != (g.stream_profile == nullptr))
         return hipErrorInvalidValue;
-    // (the int16 vector path stages int16; every other path float)
-    const int64_t nl = std::min<int64_t>(g.n_last, g.ring_len);
-    const bool dma = g.pcm16 == nullptr && g.stage >= g.block && g.stage >= nl;
-    // 16-B pieces: every tick row 16-B aligned, whole 4-sample groups that never straddle the ring wrap
-    const bool dma4 = dma && g.block % 4 == 0 && g.block <= 256 * kDma4Chunks &&
-                      g.stride % 4 == 0 && g.tick_stride % 4 == 0 && g.ring_len % 4 == 0 && g.sring_len % 4 == 0 &&
-                      ((uintptr_t)g.pcm & 15) == 0;
-    // int16 input in 16-B pieces: rows 16-B aligned, whole 8-sample groups
-    const bool vec16 = g.pcm16 != nullptr && g.block % 8 == 0 && g.block <= 512 * kPcm16Pieces &&
-                       g.stride % 8 == 0 && g.tick_stride % 8 == 0 && g.sring_len % 8 == 0 &&
-                       ((uintptr_t)g.pcm16 & 15) == 0;
-    // the DMA 3 instantiations (and only they) stage int16
-    const bool i16stage = vec16 && !dma4 && g.n_blocks <= 64 * kGateRegMax;
-    const size_t lds = 4 * gate_wave_lds(g.val_len, g.stage, i16stage ? 2 : 4) +
+    const GateFamily f = gate_family(g);
+    // the DMA 3 instantiations (and only they) stage int16; every other path float
+    const size_t lds = 4 * gate_wave_lds(g.val_len, g.stage, f.dma == 3 ? 2 : 4) +
                        2 * sizeof(PwTree) +   // + the two sub-chunk trees (k_gate_ticks)
                        (lsn ? 4 * kLsnWaveLds : 0);   // + the listener lanes' times
-    if (lsn) {   // the families with the per-stream timings and the listener lanes
-        if (g.n_blocks <= 128) {
-            if (dma4) hipLaunchKernelGGL((k_gate_ticks<2, 2, true, true>), dim3(grid), dim3(256), lds, s, g);
-            else if (vec16) hipLaunchKernelGGL((k_gate_ticks<2, 3, true, true>), dim3(grid), dim3(256), lds, s, g);
-            else if (dma) hipLaunchKernelGGL((k_gate_ticks<2, 1, true, true>), dim3(grid), dim3(256), lds, s, g);
-            else hipLaunchKernelGGL((k_gate_ticks<2, 0, true, true>), dim3(grid), dim3(256), lds, s, g);
-        } else if (g.n_blocks <= 64 * kGateRegMax) {
-            if (dma4) hipLaunchKernelGGL((k_gate_ticks<kGateRegMax, 2, true, true>), dim3(grid), dim3(256), lds, s, g);
-            else if (vec16) hipLaunchKernelGGL((k_gate_ticks<kGateRegMax, 3, true, true>), dim3(grid), dim3(256), lds, s, g);
-            else if (dma) hipLaunchKernelGGL((k_gate_ticks<kGateRegMax, 1, true, true>), dim3(grid), dim3(256), lds, s, g);
-            else hipLaunchKernelGGL((k_gate_ticks<kGateRegMax, 0, true, true>), dim3(grid), dim3(256), lds, s, g);
-        } else {
-            hipLaunchKernelGGL((k_gate_ticks<0, 0, true, true>), dim3(grid), dim3(256), lds, s, g);
-        }
-        return hipGetLastError();
-    }
-    if (g.profiles) {   // the same families with the per-stream timings
-        if (g.n_blocks <= 128) {
-            if (dma4) hipLaunchKernelGGL((k_gate_ticks<2, 2, true>), dim3(grid), dim3(256), lds, s, g);
-            else if (vec16) hipLaunchKernelGGL((k_gate_ticks<2, 3, true>), dim3(grid), dim3(256), lds, s, g);
-            else if (dma) hipLaunchKernelGGL((k_gate_ticks<2, 1, true>), dim3(grid), dim3(256), lds, s, g);
-            else hipLaunchKernelGGL((k_gate_ticks<2, 0, true>), dim3(grid), dim3(256), lds, s, g);
-        } else if (g.n_blocks <= 64 * kGateRegMax) {
-            if (dma4) hipLaunchKernelGGL((k_gate_ticks<kGateRegMax, 2, true>), dim3(grid), dim3(256), lds, s, g);
-            else if (vec16) hipLaunchKernelGGL((k_gate_ticks<kGateRegMax, 3, true>), dim3(grid), dim3(256), lds, s, g);
-            else if (dma) hipLaunchKernelGGL((k_gate_ticks<kGateRegMax, 1, true>), dim3(grid), dim3(256), lds, s, g);
-            else hipLaunchKernelGGL((k_gate_ticks<kGateRegMax, 0, true>), dim3(grid), dim3(256), lds, s, g);
-        } else {
-            hipLaunchKernelGGL((k_gate_ticks<0, 0, true>), dim3(grid), dim3(256), lds, s, g);
-        }
-        return hipGetLastError();
-    }
-    if (g.n_blocks <= 128) {
-        if (dma4) hipLaunchKernelGGL((k_gate_ticks<2, 2>), dim3(grid), dim3(256), lds, s, g);
-        else if (vec16) hipLaunchKernelGGL((k_gate_ticks<2, 3>), dim3(grid), dim3(256), lds, s, g);
-        else if (dma) hipLaunchKernelGGL((k_gate_ticks<2, 1>), dim3(grid), dim3(256), lds, s, g);
-        else hipLaunchKernelGGL((k_gate_ticks<2, 0>), dim3(grid), dim3(256), lds, s, g);
-    } else if (g.n_blocks <= 64 * kGateRegMax) {
-        if (dma4) hipLaunchKernelGGL((k_gate_ticks<kGateRegMax, 2>), dim3(grid), dim3(256), lds, s, g);
-        else if (vec16) hipLaunchKernelGGL((k_gate_ticks<kGateRegMax, 3>), dim3(grid), dim3(256), lds, s, g);
-        else if (dma) hipLaunchKernelGGL((k_gate_ticks<kGateRegMax, 1>), dim3(grid), dim3(256), lds, s, g);
-        else hipLaunchKernelGGL((k_gate_ticks<kGateRegMax, 0>), dim3(grid), dim3(256), lds, s, g);
-    } else {
-        hipLaunchKernelGGL((k_gate_ticks<0, 0>), dim3(grid), dim3(256), lds, s, g);
-    }
+    if (f.lsn) launch_gate_family<true, true>(f, grid, lds, s, g);     // the per-stream timings and the listener lanes
+    else if (f.prof) launch_gate_family<true, false>(f, grid, lds, s, g);   // the per-stream timings
+    else launch_gate_family<false, false>(f, grid, lds, s, g);
     return hipGetLastError();
 }
 

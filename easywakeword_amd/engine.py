@@ -479,6 +479,15 @@ class StreamEngine(Engine):
         check(fn(self._h, self._poll_buf.ctypes.data_as(C.POINTER(_lib.EwkEvent)), cap, C.byref(self._poll_n)))
         return self._poll_buf[: self._poll_n.value].copy()
 
+    def gate_launch_info(self) -> dict:
+        """Which gate kernel the last gate launch ran (include/ewk.h, ewk_gate_launch_info): rb, dma,
+        prof, lsn (-1 before the first launch) and block_tree_kind, last_tree_kind (0 = a leaf of
+        fewer than 8 elements, 1 = one leaf, 2 = balanced, 3 = general).  Host bookkeeping, no wait."""
+        names = ("rb", "dma", "prof", "lsn", "block_tree_kind", "last_tree_kind")
+        v = [C.c_int32(-1) for _ in names]
+        check(self._lib.ewk_gate_launch_info(self._h, *[C.byref(x) for x in v]))
+        return {n: int(x.value) for n, x in zip(names, v)}
+
     def state(self, stream: int) -> dict:
         st = _lib.EwkStreamState()
         check(self._lib.ewk_get_stream_state(self._h, int(stream), C.byref(st)))

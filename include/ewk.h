@@ -713,6 +713,21 @@ int ewk_import_streams(ewk_engine* e, const int32_t* streams, int32_t n, const e
  * 5 = the pack and unpack launches of ewk_export_streams / ewk_import_streams. */
 int ewk_profile_enable(ewk_engine* e, int32_t on);
 int ewk_profile_read(ewk_engine* e, int32_t kind, double* total_ms, int64_t* launches);
+/* Which gate kernel the engine's last gate launch ran (read-only, host bookkeeping, no wait; any
+ * pointer may be NULL).  The gate has one instantiation per family, picked from the geometry, the
+ * input's type and alignment, and whether detector profiles or listeners are set:
+ *   rb:   block-RMS slots per lane kept in registers, 2 (up to 128 blocks) or 8 (up to 512);
+ *         0 = the arrays stay in device memory
+ *   dma:  0 = the tick's samples through registers, 1 = float32 input staged by LDS-DMA in 4-byte
+ *         pieces, 2 = in 16-byte pieces, 3 = int16 input in 16-byte pieces (int16 stage)
+ *   prof, lsn: 1 when the per-stream timings / the listener lanes are compiled in
+ * all four -1 before the first launch.  block_tree_kind / last_tree_kind: how the sum over a
+ * callback block / over the last 0.1 s follows numpy's pairwise order -- 0 = one leaf of fewer
+ * than 8 elements, 1 = one leaf (at most 128), 2 = a balanced tree of at most 16 leaves, 3 = the
+ * general tree.  For tests and tuning: a change of the dispatch shows here instead of moving a
+ * workload silently onto another kernel.  EWK_EINVAL for an engine without streams. */
+int ewk_gate_launch_info(ewk_engine* e, int32_t* rb, int32_t* dma, int32_t* prof, int32_t* lsn,
+                         int32_t* block_tree_kind, int32_t* last_tree_kind);
 
 #ifdef __cplusplus
 }
