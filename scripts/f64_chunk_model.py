@@ -1,4 +1,4 @@
-"""numpy model of the chunked fp64 re-score (csrc/ewk_f64.h) -- a development check of its
+"""numpy model of the chunked fp64 re-score (csrc/ewk_rescore.h) -- a development check of its
 index maps and algebra against oracle/mfcc_ref.py, not a test of the GPU code.
 
 Per 8-frame chunk (one wave, 64 lanes, one frame at a time):
@@ -22,38 +22,40 @@ from oracle import mfcc_ref  # noqa: E402
 
 
 def stockham256(z):
-    d = z.astype(np.complex128).copy()
+    """z [..., 256] -> its DFT, by the kernel's radix-4 Stockham steps (all lanes j at once)."""
+    d = np.asarray(z, np.complex128)
+    j = np.arange(64)
+    r = np.arange(4)[:, None]
     for Ns in (1, 4, 16, 64):
-        out = np.zeros(256, np.complex128)
-        for j in range(64):
-            v = np.array([d[j + 64 * r] for r in range(4)])
-            e = j % Ns
-            v = v * np.exp(-2j * np.pi * np.arange(4) * e / (4 * Ns))
-            V = np.array([v[0] + v[1] + v[2] + v[3],
-                          v[0] - 1j * v[1] - v[2] + 1j * v[3],
-                          v[0] - v[1] + v[2] - v[3],
-                          v[0] + 1j * v[1] - v[2] - 1j * v[3]])
-            base = (j // Ns) * 4 * Ns + e
-            for r in range(4):
-                out[base + r * Ns] = V[r]
+        e = j % Ns
+        v = d[..., j[None, :] + 64 * r] * np.exp(-2j * np.pi * r * e[None, :] / (4 * Ns))   # [..., 4, 64]
+        v0, v1, v2, v3 = v[..., 0, :], v[..., 1, :], v[..., 2, :], v[..., 3, :]
+        V = np.stack([v0 + v1 + v2 + v3,
+                      v0 - 1j * v1 - v2 + 1j * v3,
+                      v0 - v1 + v2 - v3,
+                      v0 + 1j * v1 - v2 - 1j * v3], axis=-2)
+        out = np.zeros(d.shape, np.complex128)
+        out[..., ((j // Ns) * 4 * Ns + e)[None, :] + r * Ns] = V
         d = out
     return d
 
 
 def frame_logmel(x, t, win, melw):
-    """log-mel (dB, fp64) of frame t of segment x (stft center=True, constant pad)."""
+    """log-mel (dB, fp64) of frame t of segment x (stft center=True, constant pad); t may be an
+    array of frames ([n] -> [n, 128]), and may lie past the segment's last frame."""
     L = len(x)
-    q = t * 160 - 256 + np.arange(512)
-    s = np.where((q >= 0) & (q < L), x[np.clip(q, 0, L - 1)], 0.0).astype(np.float64)
+    t = np.asarray(t)
+    q = t[..., None] * 160 - 256 + np.arange(512)
+    s = np.where((q >= 0) & (q < L), np.asarray(x, np.float64)[np.clip(q, 0, L - 1)], 0.0)
     xw = s * win
-    z = xw[0::2] + 1j * xw[1::2]
+    z = xw[..., 0::2] + 1j * xw[..., 1::2]
     Z = stockham256(z)
     k = np.arange(257)
-    zk, zc = Z[k & 255], np.conj(Z[(256 - k) & 255])
+    zk, zc = Z[..., k & 255], np.conj(Z[..., (256 - k) & 255])
     E, O = 0.5 * (zk + zc), -0.5j * (zk - zc)
     X = E + np.exp(-2j * np.pi * k / 512) * O
     P = X.real ** 2 + X.imag ** 2
-    mel = melw.astype(np.float64) @ P
+    mel = P @ melw.astype(np.float64).T
     return 10.0 * np.log10(np.maximum(1e-10, mel))
 
 
@@ -70,19 +72,27 @@ def chunk_sums(lm, theta_s, W, D, first):
                 sBB=(dB * dB).sum(0), n=len(lm), mx=float(lm.max()), amb=amb)
 
 
-def model_stats(x, theta_s, W=1e-3, F=8):
+def model_stats(x, theta_s, W=2e-4, F=8):
+    """-> (mean, std, number of recomputed chunks, info) of the kernel's algebra; W is kRsWindow.
+    info: `ambiguous` (chunks holding a value within W of theta_s), `recomputed` (those, or every
+    chunk when theta is not within W of theta_s: the kernel's redo_all), `redo_all`, `max_chunk`
+    (the chunk of the segment's max), `theta`, `clamp_frac` (per chunk, the fraction of its
+    log-mel entries below theta_s: 0 is the kernel's need_b = false) and `lm` [T, 128]."""
     melw, win = mfcc_ref._tables()
     D = np.array([[(np.sqrt(1 / 128) if k == 0 else np.sqrt(2 / 128)) * np.cos(np.pi * k * (2 * m + 1) / 256)
                    for m in range(128)] for k in range(20)])
     T = 1 + len(x) // 160
-    lm = np.array([frame_logmel(x, t, win, melw) for t in range(T)])
+    lm = np.concatenate([frame_logmel(x, np.arange(t, min(t + 256, T)), win, melw) for t in range(0, T, 256)])
     parts = [chunk_sums(lm[c:c + F], theta_s, W, D, c) for c in range(0, T, F)]
-    theta = max(p["mx"] for p in parts) - 80.0
-    recomputed = 0
-    for i, p in enumerate(parts):
-        if p["amb"] or abs(theta - theta_s) > W:
-            parts[i] = chunk_sums(lm[i * F:(i + 1) * F], theta, 0.0, D, i * F)
-            recomputed += 1
+    mxs = [p["mx"] for p in parts]
+    theta = max(mxs) - 80.0
+    redo_all = not (abs(theta - theta_s) <= W)       # (as the kernel: a NaN theta_s redoes everything)
+    info = dict(ambiguous=[i for i, p in enumerate(parts) if p["amb"]], redo_all=redo_all,
+                max_chunk=int(np.argmax(mxs)), theta=theta, lm=lm,
+                clamp_frac=np.array([float(np.mean(lm[c:c + F] < theta_s)) for c in range(0, T, F)]))
+    info["recomputed"] = [i for i, p in enumerate(parts) if p["amb"] or redo_all]
+    for i in info["recomputed"]:
+        parts[i] = chunk_sums(lm[i * F:(i + 1) * F], theta, 0.0, D, i * F)
     ref0 = parts[0]["rA"] + theta * parts[0]["rB"]
     S1 = np.zeros(20)
     S2 = np.zeros(20)
@@ -94,7 +104,7 @@ def model_stats(x, theta_s, W=1e-3, F=8):
         S1 += s1 + p["n"] * dl
     mean = ref0 + S1 / T
     var = np.maximum((S2 - S1 * S1 / T) / T, 0.0)
-    return mean, np.sqrt(var), recomputed
+    return mean, np.sqrt(var), len(info["recomputed"]), info
 
 
 def rs_swz(i):
@@ -131,6 +141,6 @@ if __name__ == "__main__":
     for x in cases:
         m_ref, s_ref = mfcc_ref.extract_mfcc(x)
         th32 = float(mfcc_ref.log_mel(x.astype(np.float32)).max()) - 80.0   # an f32-ish estimate
-        m, s, rc = model_stats(x, th32)
+        m, s, rc, _ = model_stats(x, th32)
         print(f"T={1 + len(x) // 160:4d} recomputed={rc} |dmean|={np.abs(m - m_ref).max():.3e} "
               f"|dstd|={np.abs(s - s_ref).max():.3e}")

@@ -225,7 +225,7 @@ def test_extract_mfcc_keeps_the_input_dtype():
 
 
 def test_top_db_past_the_tile_record(engine):
-    """Segments longer than the per-wave tile record (kSpecTiles = 64 tiles, 1024 frames):
+    """Segments longer than the per-wave tile record (kSpecTiles = 48 tiles, 768 frames):
     taken in time order, the tiles past the record are stored unclamped and always
     recomputed when top_db bites -- a loud burst early, mid-way or at the end of 12-20 s
     of quiet noise must still equal the oracle."""
