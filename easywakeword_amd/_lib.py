@@ -48,6 +48,9 @@ EWK_PROFILE_MAX = 65536
 EWK_LISTENERS_MAX = 16       # listeners (detector profile, word) per stream
 EWK_EV_LISTENER_SHIFT = 16   # bits 16..19 of an event's flags: the listener that cut it
 EWK_CHUNK_MAX_TICKS = 64     # a chunk holds at most this many input blocks (ewk_push_chunks)
+G711_ULAW = 0                # ewk_push_g711 and friends: PCMU (mu-law) ...
+G711_ALAW = 1                # ... and PCMA (A-law) code bytes
+G711_LAWS = {"ulaw": G711_ULAW, "alaw": G711_ALAW}
 EWK_SNAPSHOT_MAGIC = 0x4E534B45   # "EKSN": a stream snapshot (ewk_export_streams)
 EWK_SNAPSHOT_VERSION = 1
 EWK_SNAP_SECTIONS = 8
@@ -75,6 +78,7 @@ EXPORTS = [
     "ewk_stream_listeners_set", "ewk_stream_listeners", "ewk_get_listener_state",
     "ewk_push_chunks", "ewk_push_chunks_pcm16", "ewk_stream_pending", "ewk_chunk_plan",
     "ewk_snapshot_plan", "ewk_snapshot_info", "ewk_export_streams", "ewk_import_streams",
+    "ewk_g711_table", "ewk_decode_g711", "ewk_push_g711", "ewk_push_streams_g711", "ewk_push_chunks_g711",
 ]
 
 
@@ -284,6 +288,13 @@ def load():
             "ewk_snapshot_info": (C.c_int, [_P, C.POINTER(EwkSnapshotLayout)]),
             "ewk_export_streams": (C.c_int, [_P, _i32p, C.c_int32, _P, _P, C.c_int64, C.c_int32]),
             "ewk_import_streams": (C.c_int, [_P, _i32p, C.c_int32, _P, _P, C.c_int64, C.c_int32]),
+            "ewk_g711_table": (C.c_int, [C.c_int32, _P]),
+            "ewk_decode_g711": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int32, C.c_int32]),
+            "ewk_push_g711": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+            "ewk_push_streams_g711": (C.c_int, [_P, _i32p, C.c_int32, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32,
+                                                C.c_int32]),
+            "ewk_push_chunks_g711": (C.c_int, [_P, _i32p, C.c_int32, _P, C.c_int64, _i64p, _i32p, C.c_int32, _P,
+                                               C.c_int32]),
         }
         for name, (res, args) in sig.items():
             fn = getattr(lib, name)

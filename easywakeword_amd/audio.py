@@ -13,9 +13,14 @@ Sources replace the PortAudio input stream of SoundBuffer (wakeword.py:438-444):
 each yields float32 blocks of ``block`` samples, one per 0.1 s tick -- or, for a source kept at
 its own sample rate (``rate=`` / ``native_rate=True`` / ``samplerate=``), the tick's samples at
 that rate, which the engine resamples on the device (StreamEngine.set_input_rate).
+
+G.711 (``g711_decode`` / ``g711_encode``, WAVE_FORMAT_ALAW / WAVE_FORMAT_MULAW files, and sources
+with ``codec="ulaw"`` / ``"alaw"``): PCMU and PCMA code bytes.  A source with a codec yields uint8
+blocks and the engine decodes them on the device (StreamEngine.push_g711 / push_chunks_g711).
 """
 from __future__ import annotations
 
+import struct
 import wave
 from typing import Iterator, Optional
 
@@ -24,7 +29,89 @@ import numpy as np
 FREQUENCY = 16000
 
 
+G711_PAD = {"ulaw": 0xFF, "alaw": 0xD5}   # the code of a zero sample (A-law: of +8, its smallest magnitude)
+_WAVE_FORMAT_G711 = {6: "alaw", 7: "ulaw"}   # WAVE_FORMAT_ALAW, WAVE_FORMAT_MULAW
+
+
+def _g711_law(law: str) -> str:
+    if law not in G711_PAD:
+        raise ValueError(f'law must be "ulaw" or "alaw", got {law!r}')
+    return law
+
+
+def g711_decode(codes, law: str) -> np.ndarray:
+    """G.711 code bytes -> int16 (ITU-T G.711; equal to audioop.ulaw2lin / alaw2lin at width 2,
+    and to the device decode, csrc/ewk_g711.h).  The float sample is the value / 32768."""
+    b = np.asarray(codes, dtype=np.uint8).astype(np.int32)
+    if _g711_law(law) == "ulaw":
+        u = ~b & 0xFF
+        t = (((u & 0xF) << 3) + 0x84) << ((u >> 4) & 7)
+        v = np.where(u & 0x80, 0x84 - t, t - 0x84)
+    else:
+        a = b ^ 0x55
+        e, m = (a >> 4) & 7, a & 0xF
+        t = np.where(e == 0, (m << 4) + 8, ((m << 4) + 0x108) << np.maximum(e - 1, 0))
+        v = np.where(a & 0x80, t, -t)
+    return v.astype(np.int16)
+
+
+_SEG_UEND = np.array([0x3F, 0x7F, 0xFF, 0x1FF, 0x3FF, 0x7FF, 0xFFF, 0x1FFF])
+_SEG_AEND = np.array([0x1F, 0x3F, 0x7F, 0xFF, 0x1FF, 0x3FF, 0x7FF, 0xFFF])
+
+
+def g711_encode(pcm16, law: str) -> np.ndarray:
+    """int16 PCM -> G.711 code bytes: the ITU / Sun g711.c encoder on the sample's upper 14
+    (mu-law) or 13 (A-law) bits, equal to audioop.lin2ulaw / lin2alaw at width 2 on every value."""
+    x = np.asarray(pcm16, dtype=np.int16).astype(np.int32)
+    if _g711_law(law) == "ulaw":
+        v = x >> 2
+        mask = np.where(v < 0, 0x7F, 0xFF)
+        v = np.minimum(np.abs(v), 8159) + (0x84 >> 2)
+        seg = np.searchsorted(_SEG_UEND, v, side="left")
+        code = np.where(seg >= 8, 0x7F, (seg << 4) | ((v >> (seg + 1)) & 0xF))
+    else:
+        v = x >> 3
+        mask = np.where(v >= 0, 0xD5, 0x55)
+        v = np.where(v >= 0, v, -v - 1)
+        seg = np.searchsorted(_SEG_AEND, v, side="left")
+        code = np.where(seg >= 8, 0x7F, (seg << 4) | ((v >> np.maximum(seg, 1)) & 0xF))
+    return (code ^ mask).astype(np.uint8)
+
+
+def _read_g711_wav(path: str):
+    """(law, channels, rate, code bytes) of a WAVE_FORMAT_ALAW / WAVE_FORMAT_MULAW file, which the
+    stdlib wave module refuses; None for every other format.  RIFF chunks parsed by hand."""
+    with open(str(path), "rb") as f:
+        raw = f.read()
+    if len(raw) < 12 or raw[:4] != b"RIFF" or raw[8:12] != b"WAVE":
+        return None
+    at, fmt, data = 12, None, None
+    while at + 8 <= len(raw):
+        cid, size = raw[at:at + 4], struct.unpack_from("<I", raw, at + 4)[0]
+        body = raw[at + 8:at + 8 + size]
+        if cid == b"fmt " and len(body) >= 16:
+            fmt = struct.unpack_from("<HHIIHH", body, 0)
+        elif cid == b"data":
+            data = body
+        at += 8 + size + (size & 1)   # chunks are word-aligned
+    if fmt is None or fmt[0] not in _WAVE_FORMAT_G711:
+        return None
+    if data is None or fmt[5] != 8 or fmt[1] < 1:
+        raise ValueError(f"{path}: a G.711 WAV needs 8 bits per sample and a data chunk")
+    return _WAVE_FORMAT_G711[fmt[0]], int(fmt[1]), int(fmt[2]), np.frombuffer(data, dtype=np.uint8)
+
+
 def load_wav(path: str, sr: int = FREQUENCY) -> np.ndarray:
+    g711 = _read_g711_wav(path)
+    if g711 is not None:   # decoded on the host: int16 / 32768, as PCM16
+        law, nch, rate, codes = g711
+        codes = codes[:len(codes) - len(codes) % nch]
+        x = g711_decode(codes, law).astype(np.float32) / np.float32(32768.0)
+        if nch > 1:
+            x = np.mean(x.reshape(-1, nch).T, axis=0).astype(np.float32)
+        if rate != sr:
+            x = resample(x, rate, sr)
+        return np.ascontiguousarray(x, dtype=np.float32)
     with wave.open(str(path), "rb") as w:
         nch, sw, rate, n = w.getnchannels(), w.getsampwidth(), w.getframerate(), w.getnframes()
         raw = w.readframes(n)
@@ -82,12 +169,18 @@ class ArraySource:
     engine is built with) and the engine resamples them on the device.
     ``read_sizes``: an int, or a sequence that is cycled -- every read yields that many input
     samples instead of a tick's (a network source's packets; the engine re-blocks them on the
-    device, StreamEngine.push_chunks)."""
+    device, StreamEngine.push_chunks).
+    ``codec``: "ulaw" or "alaw" -- `audio` holds G.711 code bytes (normally with ``rate=8000``),
+    every read yields a uint8 block for the engine to decode on the device, and the padding after
+    the end is the law's code for zero (0xFF for mu-law, 0xD5 for A-law)."""
 
     realtime = False
 
-    def __init__(self, audio, block: int = 1600, loop: bool = False, rate: int = FREQUENCY, read_sizes=None):
-        self.audio = np.ascontiguousarray(np.asarray(audio, dtype=np.float32).reshape(-1))
+    def __init__(self, audio, block: int = 1600, loop: bool = False, rate: int = FREQUENCY, read_sizes=None,
+                 codec: Optional[str] = None):
+        self.codec = None if codec is None else _g711_law(codec)
+        self.dtype, self.pad = (np.float32, 0.0) if codec is None else (np.uint8, G711_PAD[codec])
+        self.audio = np.ascontiguousarray(np.asarray(audio, dtype=self.dtype).reshape(-1))
         self.block = int(block)
         self.rate = int(rate)
         self.read_block = input_block(self.block, self.rate)
@@ -113,7 +206,7 @@ class ArraySource:
             idx = (self.pos + np.arange(n)) % len(a)
             out = a[idx]
         else:
-            out = np.zeros(n, np.float32)
+            out = np.full(n, self.pad, self.dtype)
             if self.pos < len(a):
                 chunk = a[self.pos:self.pos + n]
                 out[:len(chunk)] = chunk
@@ -137,8 +230,12 @@ class WavSource(ArraySource):
 
     def __init__(self, path: str, block: int = 1600, loop: bool = False, native_rate: bool = False):
         if native_rate:
-            with wave.open(str(path), "rb") as w:
-                rate = w.getframerate()
+            g711 = _read_g711_wav(path)
+            if g711 is not None:
+                rate = g711[2]
+            else:
+                with wave.open(str(path), "rb") as w:
+                    rate = w.getframerate()
             super().__init__(load_wav(path, sr=rate), block=block, loop=loop, rate=rate)
         else:
             super().__init__(load_wav(path), block=block, loop=loop)

@@ -18,7 +18,7 @@ SOURCES = ["ewk_mfcc.hip", "ewk_bank.hip", "ewk_gate.hip", "ewk_level3.hip", "ew
            "ewk_engine_assign.cpp", "ewk_engine_poll.cpp", "ewk_engine_resample.cpp", "ewk_engine_snapshot.cpp",
            "ewk_tables.cpp"]
 HEADERS = ["ewk_internal.h", "ewk_engine.h", "ewk_gate.h", "ewk_rescore.h", "ewk_rs_list.h", "ewk_score.h", "ewk_db64.h", "ewk_topdb_shift.h", "ewk_chunk_plan.h",
-           "ewk_snapshot.h", "ewk_snapshot_plan.h",
+           "ewk_snapshot.h", "ewk_snapshot_plan.h", "ewk_g711.h",
            os.path.join("..", "..", "include", "ewk.h")]
 LIB = os.path.join(HERE, "libewk.so")
 ARCH = os.environ.get("EWK_OFFLOAD_ARCH", "gfx950")

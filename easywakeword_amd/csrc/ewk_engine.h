@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "ewk_chunk_plan.h"
+#include "ewk_g711.h"
 #include "ewk_gate.h"
 #include "ewk_internal.h"
 #include "ewk_snapshot.h"
@@ -332,10 +333,21 @@ struct ProfScope {
     }
 };
 
-// Where the tick samples of a push are now: stream (row) r, tick t at p + r * stride + t * tick_stride.
+// What a push's samples are: float32, int16 PCM, or G.711 codes with their law (ewk_g711.h).  The
+// gate reads the first two; G.711 always goes through the resampler, which hands on float32.
+enum SampleType : int32_t { kSampleF32 = 0, kSamplePcm16 = 1, kSampleG711 = 2 };
+struct SampleKind {
+    SampleType type;
+    int32_t law;   // kSampleG711: kG711Ulaw / kG711Alaw (a chunk push with per-chunk laws: unused)
+    size_t es() const { return type == kSampleF32 ? sizeof(float) : type == kSamplePcm16 ? sizeof(int16_t) : 1; }
+};
+constexpr SampleKind kKindF32{kSampleF32, 0}, kKindPcm16{kSamplePcm16, 0};
+
+// Where the tick samples of a push are now: stream (row) r, tick t at p + r * stride + t * tick_stride
+// (in samples of `kind`).
 struct TickSrc {
     const void* p;
-    bool pcm16;   // int16 PCM, else float32
+    SampleKind kind;
     int64_t stride, tick_stride;
 };
 
@@ -373,6 +385,7 @@ int stage_stream_list(ewk_engine* e, const int32_t* streams, const int32_t* vals
 int scatter_assign(ewk_engine* e, ewk::DevBuf<int32_t>& dst, std::vector<int32_t>& mirror, const int32_t* streams,
                    const int32_t* vals, int32_t n, hipStream_t s);
 int desynchronise(ewk_engine* e, hipStream_t s);
+int check_g711(ewk_engine* e, int32_t law, const uint8_t* laws, int32_t n);   // the refusals of a G.711 push
 int send_staged(ewk_engine* e, size_t bytes, hipStream_t s);
 int gate_ticks(ewk_engine* e, const TickSrc& src, int32_t rows, int32_t n_ticks, const int32_t* d_list,
                const int32_t* streams, hipStream_t s);

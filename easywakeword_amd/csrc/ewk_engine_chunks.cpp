@@ -43,7 +43,7 @@ int ewk_stream_pending(ewk_engine* e, const int32_t* streams, int32_t n, int32_t
 // Validates the call and plans it into e->chunk_plan, on the host: everything is validated before
 // anything is enqueued or changed.
 static int plan_chunks(ewk_engine* e, const int32_t* streams, int32_t n, const void* pcm, int64_t n_pcm,
-                       const int64_t* offsets, const int32_t* counts, bool pcm16) {
+                       const int64_t* offsets, const int32_t* counts, SampleKind kind, const uint8_t* laws) {
     if (!e) return fail(EWK_EINVAL, "engine is NULL");
     if (e->n_streams <= 0) return fail(EWK_EINVAL, "engine has no streams");
     int rc = check_stream_list(e, streams, n);
@@ -51,8 +51,12 @@ static int plan_chunks(ewk_engine* e, const int32_t* streams, int32_t n, const v
     if (!offsets || !counts) return fail(EWK_EINVAL, "offsets or counts is NULL");
     if (n_pcm < 0) return fail(EWK_EINVAL, "n_pcm must be >= 0");
     if (!pcm && n_pcm > 0) return fail(EWK_EINVAL, "pcm is NULL");
-    if (!pcm16 && e->ring_es == sizeof(int16_t))
+    if (kind.type != kSamplePcm16 && e->ring_es == sizeof(int16_t))
         return fail(EWK_EINVAL, "an int16 ring (EWK_RING_I16) takes PCM16 chunks (ewk_push_chunks_pcm16)");
+    if (kind.type == kSampleG711) {
+        rc = check_g711(e, kind.law, laws, n);
+        if (rc) return rc;
+    }
     ChunkPlan& p = e->chunk_plan;
     p.in_block = e->rs_on ? e->rs_in_block : e->cfg.block;
     if (p.in_block > 0x7fffffff / (EWK_CHUNK_MAX_TICKS + 1))
@@ -76,14 +80,17 @@ static int plan_chunks(ewk_engine* e, const int32_t* streams, int32_t n, const v
 // Where everything goes: the tick rows in chunk_asm, and every chunk's first sample -- in the
 // caller's device buffer, or in the staging its host chunks are packed into.
 static void layout_chunks(ewk_engine* e, int32_t n, const int64_t* offsets, const int32_t* counts, bool device,
-                          bool pcm16) {
+                          SampleKind kind) {
     ChunkPlan& p = e->chunk_plan;
-    p.asm_total = chunk_row_layout(kChunkAlign / (int64_t)e->ring_es, p.in_block, p.n_groups, p.group_ticks,
+    // (a G.711 unit is 16 codes into 64 bytes of float32: its rows start on 64 bytes, so that the
+    // staged chunks' phases, taken modulo kChunkAlign codes, agree with their destinations')
+    const int64_t row_align = kind.type == kSampleG711 ? 2 * kChunkAlign : kChunkAlign;
+    p.asm_total = chunk_row_layout(row_align / (int64_t)e->ring_es, p.in_block, p.n_groups, p.group_ticks,
                                    p.group_first, p.group_base);
     p.stage_total = 0;
     if (device) std::copy(offsets, offsets + n, p.src_at.begin());
     else
-        p.stage_total = chunk_stage_layout(kChunkAlign / (int64_t)(pcm16 ? sizeof(int16_t) : sizeof(float)), n,
+        p.stage_total = chunk_stage_layout(kChunkAlign / (int64_t)kind.es(), n,
                                            p.pending.data(), counts, p.src_at.data());
 }
 
@@ -102,11 +109,11 @@ static int ensure_chunk_state(ewk_engine* e, hipStream_t s) {
 
 // Host chunks, packed into the pinned staging as laid out (the gaps zeroed: they are copied too)
 // and sent with one copy.
-static int stage_host_chunks(ewk_engine* e, const void* pcm, bool pcm16, const int64_t* offsets, const int32_t* counts,
+static int stage_host_chunks(ewk_engine* e, const void* pcm, SampleKind kind, const int64_t* offsets, const int32_t* counts,
                              int32_t n, hipStream_t s) {
     const ChunkPlan& p = e->chunk_plan;
     if (p.stage_total == 0) return EWK_OK;
-    const size_t es = pcm16 ? sizeof(int16_t) : sizeof(float);
+    const size_t es = kind.es();
     HIP_TRY(e->pcm_stage.reserve((size_t)p.stage_total * es));   // (and the previous DMA is done)
     unsigned char* h = e->pcm_stage.p;
     int64_t end = 0;
@@ -120,9 +127,11 @@ static int stage_host_chunks(ewk_engine* e, const void* pcm, bool pcm16, const i
 }
 
 // Descriptors: the ticking chunks in plan order (the gate's index lists follow it, *d_list), then
-// the appending ones; a chunk without samples needs none.  *n_desc == 0: nothing was sent.
-static int send_descriptors(ewk_engine* e, const int32_t* streams, const int32_t* counts, int32_t n, hipStream_t s,
-                            int32_t* n_desc, const int32_t** d_list) {
+// the appending ones; a chunk without samples needs none.  *n_desc == 0: nothing was sent.  A G.711
+// chunk's descriptor carries its law: laws[i], or the call's.
+static int send_descriptors(ewk_engine* e, const int32_t* streams, const int32_t* counts, int32_t n, SampleKind kind,
+                            const uint8_t* laws, hipStream_t s, int32_t* n_desc, const int32_t** d_list) {
+    auto law_of = [&](int32_t i) -> int32_t { return kind.type != kSampleG711 ? 0 : laws ? laws[i] : kind.law; };
     const ChunkPlan& p = e->chunk_plan;
     const size_t list_at = (size_t)e->n_streams * sizeof(ChunkDesc);
     HIP_TRY(e->chunk_stage.reserve(list_at + (size_t)e->n_streams * sizeof(int32_t)));   // (and the previous push's have left it)
@@ -133,12 +142,12 @@ static int send_descriptors(ewk_engine* e, const int32_t* streams, const int32_t
         for (int32_t k = p.group_first[g]; k < p.group_first[g + 1]; ++k) {
             const int32_t i = p.order[k];
             const int64_t row = p.group_base[g] + (int64_t)(k - p.group_first[g]) * p.group_ticks[g] * p.in_block;
-            h_desc[nd++] = ChunkDesc{p.src_at[i], row, streams[i], counts[i], p.pending[i], 0};
+            h_desc[nd++] = ChunkDesc{p.src_at[i], row, streams[i], counts[i], p.pending[i], law_of(i)};
             h_list[k] = streams[i];
         }
     for (int32_t i = 0; i < n; ++i)
         if (p.ticks[i] == 0 && counts[i] > 0)
-            h_desc[nd++] = ChunkDesc{p.src_at[i], 0, streams[i], counts[i], p.pending[i], 0};
+            h_desc[nd++] = ChunkDesc{p.src_at[i], 0, streams[i], counts[i], p.pending[i], law_of(i)};
     *n_desc = nd;
     if (nd == 0) return EWK_OK;
     int32_t* list = reinterpret_cast<int32_t*>(e->d_chunk.p + list_at);
@@ -151,7 +160,7 @@ static int send_descriptors(ewk_engine* e, const int32_t* streams, const int32_t
 }
 
 // The one assembly launch: carry rows and chunks into tick rows, the rest back into the carry rows.
-static int assemble_chunks(ewk_engine* e, const void* d_src, int32_t n_desc, bool pcm16, hipStream_t s) {
+static int assemble_chunks(ewk_engine* e, const void* d_src, int32_t n_desc, SampleKind kind, hipStream_t s) {
     const ChunkPlan& p = e->chunk_plan;
     ChunkArgs a;
     memset(&a, 0, sizeof(a));
@@ -162,7 +171,8 @@ static int assemble_chunks(ewk_engine* e, const void* d_src, int32_t n_desc, boo
     a.n = n_desc;
     a.in_block = p.in_block;
     a.max_ticks = p.n_groups ? p.group_ticks[p.n_groups - 1] : 1;
-    a.src16 = pcm16;
+    a.src16 = kind.type == kSamplePcm16;
+    a.src8 = kind.type == kSampleG711;
     a.out16 = e->ring_es == sizeof(int16_t);
     ProfScope ps(e, 4, s);
     HIP_TRY(launch_chunk_assemble(a, s));
@@ -184,7 +194,7 @@ static int gate_groups(ewk_engine* e, const int32_t* streams, const int32_t* d_l
     for (int32_t k = 0; k < p.n_ticking; ++k) p.order[k] = streams[p.order[k]];
     for (int32_t g = 0; g < p.n_groups; ++g) {
         const int32_t first = p.group_first[g], rows = p.group_first[g + 1] - first, nt = p.group_ticks[g];
-        TickSrc src{e->chunk_asm.p + p.group_base[g] * e->ring_es, e->ring_es == sizeof(int16_t),
+        TickSrc src{e->chunk_asm.p + p.group_base[g] * e->ring_es, e->ring_es == sizeof(int16_t) ? kKindPcm16 : kKindF32,
                     (int64_t)nt * p.in_block, p.in_block};
         int rc = e->rs_on ? resample_ticks(e, &src, rows, nt, d_list + first, s) : EWK_OK;
         if (rc == EWK_OK) rc = gate_ticks(e, src, rows, nt, d_list + first, p.order.data() + first, s);
@@ -194,21 +204,22 @@ static int gate_groups(ewk_engine* e, const int32_t* streams, const int32_t* d_l
 }
 
 static int push_chunks_impl(ewk_engine* e, const int32_t* streams, int32_t n, const void* pcm, int64_t n_pcm,
-                            const int64_t* offsets, const int32_t* counts, int32_t flags, bool pcm16) {
+                            const int64_t* offsets, const int32_t* counts, int32_t flags, SampleKind kind,
+                            const uint8_t* laws = nullptr) {
     const bool device = (flags & EWK_PUSH_DEVICE) != 0;
-    int rc = plan_chunks(e, streams, n, pcm, n_pcm, offsets, counts, pcm16);
+    int rc = plan_chunks(e, streams, n, pcm, n_pcm, offsets, counts, kind, laws);
     if (rc) return rc;
-    layout_chunks(e, n, offsets, counts, device, pcm16);
+    layout_chunks(e, n, offsets, counts, device, kind);
     HIP_TRY(hipSetDevice(e->device));
     hipStream_t s = e->stream;
     rc = desynchronise(e, s);
     if (rc == EWK_OK) rc = ensure_chunk_state(e, s);
-    if (rc == EWK_OK && !device) rc = stage_host_chunks(e, pcm, pcm16, offsets, counts, n, s);
+    if (rc == EWK_OK && !device) rc = stage_host_chunks(e, pcm, kind, offsets, counts, n, s);
     int32_t n_desc = 0;
     const int32_t* d_list = nullptr;
-    if (rc == EWK_OK) rc = send_descriptors(e, streams, counts, n, s, &n_desc, &d_list);
+    if (rc == EWK_OK) rc = send_descriptors(e, streams, counts, n, kind, laws, s, &n_desc, &d_list);
     if (rc || n_desc == 0) return rc;   // (no samples at all)
-    rc = assemble_chunks(e, device ? pcm : e->push_stage.p, n_desc, pcm16, s);
+    rc = assemble_chunks(e, device ? pcm : e->push_stage.p, n_desc, kind, s);
     if (rc) return rc;
     update_pending(e, streams, n);
     if (e->chunk_plan.n_groups == 0) return EWK_OK;   // nobody ticks: the assembly alone (a poll finds the banks as they were)
@@ -217,10 +228,16 @@ static int push_chunks_impl(ewk_engine* e, const int32_t* streams, int32_t n, co
 
 int ewk_push_chunks(ewk_engine* e, const int32_t* streams, int32_t n, const float* pcm, int64_t n_pcm,
                     const int64_t* offsets, const int32_t* counts, int32_t flags) {
-    return push_chunks_impl(e, streams, n, pcm, n_pcm, offsets, counts, flags, false);
+    return push_chunks_impl(e, streams, n, pcm, n_pcm, offsets, counts, flags, kKindF32);
 }
 
 int ewk_push_chunks_pcm16(ewk_engine* e, const int32_t* streams, int32_t n, const int16_t* pcm, int64_t n_pcm,
                           const int64_t* offsets, const int32_t* counts, int32_t flags) {
-    return push_chunks_impl(e, streams, n, pcm, n_pcm, offsets, counts, flags, true);
+    return push_chunks_impl(e, streams, n, pcm, n_pcm, offsets, counts, flags, kKindPcm16);
+}
+
+int ewk_push_chunks_g711(ewk_engine* e, const int32_t* streams, int32_t n, const uint8_t* pcm, int64_t n_pcm,
+                         const int64_t* offsets, const int32_t* counts, int32_t law, const uint8_t* laws,
+                         int32_t flags) {
+    return push_chunks_impl(e, streams, n, pcm, n_pcm, offsets, counts, flags, SampleKind{kSampleG711, law}, laws);
 }

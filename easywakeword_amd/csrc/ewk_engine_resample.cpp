@@ -79,7 +79,9 @@ int ewk::resample_ticks(ewk_engine* e, TickSrc* src, int32_t rows, int32_t n_tic
         HIP_TRY(e->rs_out.reserve(per_stream * rows));
     }
     ResampleArgs r = filter_args(e->rs_in);
-    if (src->pcm16) r.in16 = static_cast<const int16_t*>(src->p);
+    ResampleG711 g{nullptr, 0};
+    if (src->kind.type == kSampleG711) g = ResampleG711{static_cast<const uint8_t*>(src->p), src->kind.law};
+    else if (src->kind.type == kSamplePcm16) r.in16 = static_cast<const int16_t*>(src->p);
     else r.in = static_cast<const float*>(src->p);
     r.stride = src->stride;
     r.tick_stride = src->tick_stride;
@@ -95,11 +97,11 @@ int ewk::resample_ticks(ewk_engine* e, TickSrc* src, int32_t rows, int32_t n_tic
     r.n_zero = (e->rs_flags.p || e->rs_fresh) ? e->rs_delay : 0;
     {
         ProfScope ps(e, 3, s);
-        HIP_TRY(launch_resample(r, s));
-        HIP_TRY(launch_resample_save(r, e->rs_hist.p, e->rs_flags.p, s));
+        HIP_TRY(launch_resample(r, s, g));
+        HIP_TRY(launch_resample_save(r, e->rs_hist.p, e->rs_flags.p, s, g));
     }
     if (!d_list) e->rs_fresh = false;   // (a subset push made the flags: rs_fresh is not read again)
-    *src = TickSrc{e->rs_out.p, false, (int64_t)per_stream, e->cfg.block};
+    *src = TickSrc{e->rs_out.p, kKindF32, (int64_t)per_stream, e->cfg.block};
     return EWK_OK;
 }
 

@@ -607,3 +607,35 @@ int ewk_decode_pcm16(ewk_engine* e, const int16_t* in, int64_t n, float* out, in
     HIP_TRY(hipStreamSynchronize(s));
     return EWK_OK;
 }
+
+int ewk_g711_table(int32_t law, int16_t* out256) {
+    if (law != EWK_G711_ULAW && law != EWK_G711_ALAW)
+        return fail(EWK_EINVAL, "law = " + std::to_string(law) + " is neither EWK_G711_ULAW (0) nor EWK_G711_ALAW (1)");
+    if (!out256) return fail(EWK_EINVAL, "NULL argument");
+    for (uint32_t b = 0; b < 256; ++b) out256[b] = (int16_t)g711_decode(b, law);
+    return EWK_OK;
+}
+
+int ewk_decode_g711(ewk_engine* e, const uint8_t* in, int64_t n, float* out, int32_t law, int32_t flags) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (n < 0) return fail(EWK_EINVAL, "negative size");
+    if (law != EWK_G711_ULAW && law != EWK_G711_ALAW)
+        return fail(EWK_EINVAL, "law = " + std::to_string(law) + " is neither EWK_G711_ULAW (0) nor EWK_G711_ALAW (1)");
+    if (n == 0) return EWK_OK;
+    if (!in || !out) return fail(EWK_EINVAL, "NULL argument");
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t s = e->stream;
+    if (flags & EWK_PCM_DEVICE) {   // both pointers device memory; asynchronous
+        HIP_TRY(launch_decode_g711(in, out, n, law, s));
+        return EWK_OK;
+    }
+    DevBuf<uint8_t> d_in;
+    DevBuf<float> d_out;
+    HIP_TRY(d_in.reserve(n));
+    HIP_TRY(d_out.reserve(n));
+    HIP_TRY(hipMemcpyAsync(d_in.p, in, n, hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_decode_g711(d_in.p, d_out.p, n, law, s));
+    HIP_TRY(hipMemcpyAsync(out, d_out.p, n * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return EWK_OK;
+}

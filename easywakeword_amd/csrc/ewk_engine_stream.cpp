@@ -225,7 +225,7 @@ static int score_pending(ewk_engine* e, hipStream_t ss, const int32_t* n_events)
 // asynchronously on s -- the caller's buffer may die as soon as we return.
 static int stage_host_ticks(ewk_engine* e, TickSrc* src, int32_t rows, int32_t n_ticks, int64_t in_block,
                             hipStream_t s) {
-    const size_t es = src->pcm16 ? sizeof(int16_t) : sizeof(float);
+    const size_t es = src->kind.es();
     const unsigned char* pcm = static_cast<const unsigned char*>(src->p);
     const size_t per_stream = (size_t)n_ticks * in_block;
     const size_t bytes = per_stream * rows * es;
@@ -236,7 +236,7 @@ static int stage_host_ticks(ewk_engine* e, TickSrc* src, int32_t rows, int32_t n
                    pcm + ((size_t)st * src->stride + (size_t)t * src->tick_stride) * es, in_block * es);
     int rc = send_staged(e, bytes, s);
     if (rc) return rc;
-    *src = TickSrc{e->push_stage.p, src->pcm16, (int64_t)per_stream, in_block};
+    *src = TickSrc{e->push_stage.p, src->kind, (int64_t)per_stream, in_block};
     return EWK_OK;
 }
 
@@ -346,10 +346,26 @@ static int check_nothing_pending(ewk_engine* e, const int32_t* streams, int32_t 
     return EWK_OK;
 }
 
+// What a G.711 push needs beyond a PCM16 one (host only): a law of ewk.h -- `law`, or every entry of
+// `laws` [n] when given -- and an input rate, since the codes are 8 kHz samples and the gate reads
+// cfg.sample_rate ones.  (An int16 ring was refused before: it cannot have a rate.)
+int ewk::check_g711(ewk_engine* e, int32_t law, const uint8_t* laws, int32_t n) {
+    if (!laws && law != EWK_G711_ULAW && law != EWK_G711_ALAW)
+        return fail(EWK_EINVAL, "law = " + std::to_string(law) + " is neither EWK_G711_ULAW (0) nor EWK_G711_ALAW (1)");
+    for (int32_t i = 0; laws && i < n; ++i)
+        if (laws[i] != EWK_G711_ULAW && laws[i] != EWK_G711_ALAW)
+            return fail(EWK_EINVAL, "laws[" + std::to_string(i) + "] = " + std::to_string(laws[i]) +
+                                        " is neither EWK_G711_ULAW (0) nor EWK_G711_ALAW (1)");
+    if (!e->rs_on)
+        return fail(EWK_EINVAL, "a G.711 push needs an input rate: the codes are samples at the source's rate "
+                                "(8000 Hz for PCMU / PCMA), set it with ewk_set_input_rate first");
+    return EWK_OK;
+}
+
 // streams == nullptr: a tick for every stream (row s of pcm is stream s); else rows 0..n_list-1
 // are the ticks of streams[0..n_list) (ewk_push_streams).
 static int push_impl(ewk_engine* e, const void* pcm_any, int64_t stride, int64_t tick_stride, int32_t n_ticks,
-                     int32_t flags, bool pcm16, const int32_t* streams = nullptr, int32_t n_list = 0) {
+                     int32_t flags, SampleKind kind, const int32_t* streams = nullptr, int32_t n_list = 0) {
     if (!e) return fail(EWK_EINVAL, "engine is NULL");
     if (e->n_streams <= 0) return fail(EWK_EINVAL, "engine has no streams");
     if (streams || n_list) {   // (validated before anything is enqueued or changed)
@@ -359,8 +375,12 @@ static int push_impl(ewk_engine* e, const void* pcm_any, int64_t stride, int64_t
     const int32_t rows = streams ? n_list : e->n_streams;
     if (!pcm_any) return fail(EWK_EINVAL, "pcm is NULL");
     if (n_ticks <= 0) return fail(EWK_EINVAL, "n_ticks must be positive");
-    if (!pcm16 && e->ring_es == sizeof(int16_t))
+    if (kind.type != kSamplePcm16 && e->ring_es == sizeof(int16_t))
         return fail(EWK_EINVAL, "an int16 ring (EWK_RING_I16) takes PCM16 pushes (ewk_push_pcm16)");
+    if (kind.type == kSampleG711) {
+        int rc = check_g711(e, kind.law, nullptr, 0);
+        if (rc) return rc;
+    }
     // with an input rate set (ewk_set_input_rate) a tick is in_block samples at that rate
     const int64_t in_block = e->rs_on ? e->rs_in_block : e->cfg.block;
     if (stride < in_block && rows > 1)
@@ -377,7 +397,7 @@ static int push_impl(ewk_engine* e, const void* pcm_any, int64_t stride, int64_t
         if (rc == EWK_OK) rc = stage_stream_list(e, streams, nullptr, n_list, s);
     }
     const int32_t* d_list = streams ? e->d_ids.p : nullptr;
-    TickSrc src{pcm_any, pcm16, stride, tick_stride};
+    TickSrc src{pcm_any, kind, stride, tick_stride};
     if (rc == EWK_OK && !(flags & EWK_PUSH_DEVICE)) rc = stage_host_ticks(e, &src, rows, n_ticks, in_block, s);
     if (rc == EWK_OK && e->rs_on) rc = resample_ticks(e, &src, rows, n_ticks, d_list, s);
     if (rc == EWK_OK) rc = gate_ticks(e, src, rows, n_ticks, d_list, streams, s);
@@ -398,7 +418,7 @@ int ewk::gate_ticks(ewk_engine* e, const TickSrc& src, int32_t rows, int32_t n_t
     // Segments must be scored before the ring overwrites them: <= ticks_per_launch ticks per gate launch.
     for (int32_t t0 = 0; t0 < n_ticks; t0 += e->ticks_per_launch) {
         const int32_t nt = std::min<int32_t>(e->ticks_per_launch, n_ticks - t0);
-        if (src.pcm16) g.pcm16 = static_cast<const int16_t*>(src.p) + (int64_t)t0 * src.tick_stride;
+        if (src.kind.type == kSamplePcm16) g.pcm16 = static_cast<const int16_t*>(src.p) + (int64_t)t0 * src.tick_stride;
         else g.pcm = static_cast<const float*>(src.p) + (int64_t)t0 * src.tick_stride;
         g.n_ticks = nt;
         g.own_clock = e->desync ? 1 : 0;
@@ -423,34 +443,45 @@ int ewk::gate_ticks(ewk_engine* e, const TickSrc& src, int32_t rows, int32_t n_t
 }
 
 int ewk_push(ewk_engine* e, const float* pcm, int64_t stride, int32_t flags) {
-    return push_impl(e, pcm, stride, 0, 1, flags, false);
+    return push_impl(e, pcm, stride, 0, 1, flags, kKindF32);
 }
 
 int ewk_push_many(ewk_engine* e, const float* pcm, int64_t stride, int64_t tick_stride, int32_t n_ticks,
                   int32_t flags) {
-    return push_impl(e, pcm, stride, tick_stride, n_ticks, flags, false);
+    return push_impl(e, pcm, stride, tick_stride, n_ticks, flags, kKindF32);
 }
 
 int ewk_push_pcm16(ewk_engine* e, const int16_t* pcm, int64_t stride, int32_t flags) {
-    return push_impl(e, pcm, stride, 0, 1, flags, true);
+    return push_impl(e, pcm, stride, 0, 1, flags, kKindPcm16);
 }
 
 int ewk_push_many_pcm16(ewk_engine* e, const int16_t* pcm, int64_t stride, int64_t tick_stride, int32_t n_ticks,
                         int32_t flags) {
-    return push_impl(e, pcm, stride, tick_stride, n_ticks, flags, true);
+    return push_impl(e, pcm, stride, tick_stride, n_ticks, flags, kKindPcm16);
 }
 
 // ---------------------------------------------------------------- stream lifecycle
 int ewk_push_streams(ewk_engine* e, const int32_t* streams, int32_t n, const float* pcm, int64_t stride,
                      int64_t tick_stride, int32_t n_ticks, int32_t flags) {
     if (e && !streams) return fail(EWK_EINVAL, "streams is NULL");
-    return push_impl(e, pcm, stride, tick_stride, n_ticks, flags, false, streams, n);
+    return push_impl(e, pcm, stride, tick_stride, n_ticks, flags, kKindF32, streams, n);
 }
 
 int ewk_push_streams_pcm16(ewk_engine* e, const int32_t* streams, int32_t n, const int16_t* pcm, int64_t stride,
                            int64_t tick_stride, int32_t n_ticks, int32_t flags) {
     if (e && !streams) return fail(EWK_EINVAL, "streams is NULL");
-    return push_impl(e, pcm, stride, tick_stride, n_ticks, flags, true, streams, n);
+    return push_impl(e, pcm, stride, tick_stride, n_ticks, flags, kKindPcm16, streams, n);
+}
+
+int ewk_push_g711(ewk_engine* e, const uint8_t* pcm, int64_t stride, int64_t tick_stride, int32_t n_ticks, int32_t law,
+                  int32_t flags) {
+    return push_impl(e, pcm, stride, tick_stride, n_ticks, flags, SampleKind{kSampleG711, law});
+}
+
+int ewk_push_streams_g711(ewk_engine* e, const int32_t* streams, int32_t n, const uint8_t* pcm, int64_t stride,
+                          int64_t tick_stride, int32_t n_ticks, int32_t law, int32_t flags) {
+    if (e && !streams) return fail(EWK_EINVAL, "streams is NULL");
+    return push_impl(e, pcm, stride, tick_stride, n_ticks, flags, SampleKind{kSampleG711, law}, streams, n);
 }
 
 int ewk_reset_stream_list(ewk_engine* e, const int32_t* streams, int32_t n) {

@@ -248,6 +248,8 @@ struct L3Args {
 };
 hipError_t launch_normalize(const L3Args& a, hipStream_t s);
 hipError_t launch_decode_pcm16(const int16_t* in, float* out, int64_t n, hipStream_t s);
+// G.711 codes (ewk_g711.h) -> float32, any alignment of `in` and `out`
+hipError_t launch_decode_g711(const uint8_t* in, float* out, int64_t n, int32_t law, hipStream_t s);
 
 // Input-rate resampler (ewk_resample.hip): polyphase FIR in_rate -> cfg.sample_rate with the
 // filter of audio.resample (ewk_tables.cpp: up = out / gcd, down = in / gcd, half = 10 *
@@ -266,7 +268,7 @@ constexpr int kRsMaxThreads = 1024;  // a workgroup covers whole periods of `up`
 constexpr int kRsMaxSpan = 12288;    // floats of input a workgroup stages in LDS (48 KB)
 struct ResampleArgs {
     const float* in;          // float32 input, or
-    const int16_t* in16;      // int16 PCM (x / 32768)
+    const int16_t* in16;      // int16 PCM (x / 32768), or ResampleG711 below
     int64_t stride;           // samples between rows (streams)
     int64_t tick_stride;      // samples between the ticks of a row
     int64_t in_block;         // samples per tick (one-shot: n_in)
@@ -289,12 +291,21 @@ struct ResampleArgs {
     // since their history was cleared); launch_resample_save clears the flags of its rows
     const uint8_t* fresh;
 };
+// G.711 input of a launch (ResampleArgs::in and in16 nullptr then): one code byte per sample at p,
+// indexed as `in`, decoded with `law` (ewk_g711.h) on the way into LDS.  p == nullptr: none.  It
+// travels beside ResampleArgs, not in it, and runs instantiations of its own: the float32 / PCM16
+// launches keep the argument layout and the code they had.
+struct ResampleG711 {
+    const uint8_t* p;
+    int32_t law;
+};
 int resample_threads(int32_t up);   // workgroup size: a multiple of up (0: up > kRsMaxThreads)
 int64_t resample_span(int32_t up, int32_t down, int32_t J, int32_t threads);
-hipError_t launch_resample(const ResampleArgs& a, hipStream_t s);
+hipError_t launch_resample(const ResampleArgs& a, hipStream_t s, ResampleG711 g = {nullptr, 0});
 // hist[r][k] = X(n_in - H + k): the tail of a push, saved once every workgroup of launch_resample
 // has read the old one (stream order); fresh: nullptr or a.fresh
-hipError_t launch_resample_save(const ResampleArgs& a, float* hist, uint8_t* fresh, hipStream_t s);
+hipError_t launch_resample_save(const ResampleArgs& a, float* hist, uint8_t* fresh, hipStream_t s,
+                                ResampleG711 g = {nullptr, 0});
 
 // Packet ingest (ewk_chunks.hip): one launch per ewk_push_chunks* call re-blocks the call's
 // chunks.  Stream d.stream holds d.pending < in_block samples in its carry row
@@ -302,18 +313,19 @@ hipError_t launch_resample_save(const ResampleArgs& a, float* hist, uint8_t* fre
 // T = (d.pending + d.count) / in_block >= 1 the first T * in_block samples of carry ++ chunk
 // become the tick rows out[d.row + t * in_block ..], t < T, and the rest (from the chunk's tail
 // alone) the new carry; with T = 0 the chunk is appended to the carry at d.pending.  Carry and
-// rows have the ring's sample type, PCM16 into float is decoded as x / 32768.
+// rows have the ring's sample type, PCM16 into float is decoded as x / 32768, G.711 into float
+// with the chunk's own law (ewk_g711.h): a call may mix PCMU and PCMA streams.
 struct ChunkDesc {
     int64_t src;       // first sample of the chunk (elements of the source type)
     int64_t row;       // first sample of the chunk's tick row 0 in `out` (elements; unused without a tick)
     int32_t stream;
     int32_t count;
     int32_t pending;   // before the push
-    int32_t pad;
+    int32_t law;       // G.711 sources: the chunk's law (kG711Ulaw / kG711Alaw); else 0
 };
 static_assert(sizeof(ChunkDesc) == 32, "chunk descriptors are staged as bytes");
 struct ChunkArgs {
-    const void* src;          // float32, or int16 with src16
+    const void* src;          // float32, int16 with src16, or G.711 bytes with src8
     void* out;                // tick rows: float32, or int16 with out16
     void* carry;              // [n_streams][in_block], the type of out
     const ChunkDesc* desc;    // [n]
@@ -321,6 +333,7 @@ struct ChunkArgs {
     int32_t in_block;
     int32_t max_ticks;        // the largest T of the call (the launch's grid.y, at least 1)
     int32_t src16, out16;     // (float32 into int16 does not exist: an int16 ring takes PCM16)
+    int32_t src8;             // (G.711 into int16 neither: it needs an input rate, which an int16 ring refuses)
 };
 hipError_t launch_chunk_assemble(const ChunkArgs& a, hipStream_t s);
 

@@ -12,11 +12,14 @@
 //     pairwise tree evaluated lane-parallel (split top-down, combined bottom-up).
 //   * k_decode_pcm16: librosa.load / soundfile / PortAudio int16 -> float32
 //     (x / 32768, exact), the WAV/PCM16 ingest of SURVEY.md 8f.2.
+//   * k_decode_g711: PCMU / PCMA code bytes -> float32 (ewk_g711.h, exact), the one-shot
+//     decode of ewk_decode_g711.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include <algorithm>
 
+#include "ewk_g711.h"
 #include "ewk_internal.h"
 
 #pragma clang fp contract(off)
@@ -231,6 +234,48 @@ hipError_t launch_decode_pcm16(const int16_t* in, float* out, int64_t n, hipStre
     if (n <= 0) return hipSuccess;
     const int64_t blocks = std::min<int64_t>((n + 255) / 256, 8 * 256 * 8);
     hipLaunchKernelGGL(k_decode_pcm16, dim3((unsigned)blocks), dim3(256), 0, s, in, out, n);
+    return hipGetLastError();
+}
+
+// G.711 codes -> float32 (ewk_g711.h), `in` at any byte: a scalar head up to the source's 16-byte
+// alignment, units of one 16-byte load (16 codes) stored as four 16-byte vectors where the output
+// is aligned there too (else sample by sample), and a scalar tail.  Reads stay inside [in, in + n),
+// writes inside [out, out + n).
+__global__ __launch_bounds__(256) void k_decode_g711(const uint8_t* __restrict__ in, float* __restrict__ out,
+                                                     int64_t n, int32_t law) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t head = (int64_t)((16 - ((uintptr_t)in & 15)) & 15);
+    head = head < n ? head : n;
+    const int64_t units = (n - head) / 16;
+    for (int64_t i = gid; i < head; i += stride) out[i] = g711_sample(in[i], law);
+    const bool out_vec = ((uintptr_t)(out + head) & 15) == 0;
+    for (int64_t u = gid; u < units; u += stride) {
+        const uint4 raw = *reinterpret_cast<const uint4*>(in + head + u * 16);
+        uint8_t c[16];
+        __builtin_memcpy(c, &raw, 16);
+        float v[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) v[j] = g711_sample(c[j], law);
+        float* o = out + head + u * 16;
+        if (out_vec) {
+            float4 w[4];
+            __builtin_memcpy(w, v, sizeof(w));
+#pragma unroll
+            for (int j = 0; j < 4; ++j) reinterpret_cast<float4*>(o)[j] = w[j];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) o[j] = v[j];
+        }
+    }
+    for (int64_t i = head + units * 16 + gid; i < n; i += stride) out[i] = g711_sample(in[i], law);
+}
+
+hipError_t launch_decode_g711(const uint8_t* in, float* out, int64_t n, int32_t law, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    if (law != kG711Ulaw && law != kG711Alaw) return hipErrorInvalidValue;
+    const int64_t blocks = std::min<int64_t>((n / 16 + 255) / 256 + 1, 8 * 256 * 8);
+    hipLaunchKernelGGL(k_decode_g711, dim3((unsigned)blocks), dim3(256), 0, s, in, out, n, law);
     return hipGetLastError();
 }
 

@@ -28,6 +28,14 @@ def _f32(audio) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def _law(law) -> int:
+    """"ulaw" / "alaw" -> EWK_G711_ULAW / EWK_G711_ALAW."""
+    try:
+        return _lib.G711_LAWS[law]
+    except (KeyError, TypeError):
+        raise ValueError(f'law must be "ulaw" or "alaw", got {law!r}') from None
+
+
 def _pack(segs):
     """Ragged float32 arrays -> (pcm, offsets int64, lengths int32)."""
     n = len(segs)
@@ -329,6 +337,15 @@ class Engine:
                                              out.ctypes.data_as(C.c_void_p), 0))
         return out
 
+    def decode_g711(self, codes: np.ndarray, law: str) -> np.ndarray:
+        """G.711 code bytes (`law`: "ulaw" or "alaw") -> float32 (v / 32768, v the code's 16-bit
+        value: audio.g711_decode) on the GPU."""
+        a = np.ascontiguousarray(codes, dtype=np.uint8)
+        out = np.zeros(a.shape, np.float32)
+        check(self._lib.ewk_decode_g711(self._h, a.ctypes.data_as(C.c_void_p), a.size,
+                                        out.ctypes.data_as(C.c_void_p), _law(law), 0))
+        return out
+
     def resample(self, audio, orig_sr: int) -> np.ndarray:
         """`audio` at orig_sr Hz -> 16 kHz float32 on the GPU: the arithmetic of
         easywakeword_amd.audio.resample (polyphase Kaiser FIR, float64 accumulation),
@@ -426,6 +443,20 @@ class StreamEngine(Engine):
             check(self._lib.ewk_push_many_pcm16(self._h, a.ctypes.data_as(C.c_void_p), a.shape[1], self.input_block,
                                                 nt, 0))
 
+    def push_g711(self, codes: np.ndarray, law: str) -> None:
+        """Ticks of G.711 code bytes, uint8 [n_streams, n_ticks * input_block] (host), `law` "ulaw"
+        (PCMU) or "alaw" (PCMA): decoded inside the device resampler, so an input rate must be set
+        (set_input_rate(8000) for telephony).  The engine computes what push_pcm16 of
+        audio.g711_decode(codes, law) computes, bit for bit."""
+        a = np.ascontiguousarray(codes, dtype=np.uint8)
+        if a.ndim != 2 or a.shape[0] != self.n_streams or a.shape[1] % self.input_block:
+            raise ValueError("codes must be [n_streams, n_ticks*block]" if self.input_block == self.block else
+                             f"codes must be [n_streams, n_ticks*{self.input_block}] at {self.input_rate} Hz")
+        nt = a.shape[1] // self.input_block
+        if nt:
+            check(self._lib.ewk_push_g711(self._h, a.ctypes.data_as(C.c_void_p), a.shape[1], self.input_block,
+                                          nt, _law(law), 0))
+
     def normalize_events(self, events: np.ndarray) -> list:
         """Level-3 pre-processing of polled events straight from the rings (float64 per event)."""
         ev = np.ascontiguousarray(events, dtype=_lib.EVENT_DTYPE)
@@ -464,6 +495,11 @@ class StreamEngine(Engine):
         """Device-resident int16 PCM ticks (indexing as push_device, 2-byte samples)."""
         check(self._lib.ewk_push_many_pcm16(self._h, C.c_void_p(ptr), int(stride), int(tick_stride), int(n_ticks),
                                             _lib.EWK_PUSH_DEVICE))
+
+    def push_device_g711(self, ptr: int, stride: int, tick_stride: int, n_ticks: int, law: str) -> None:
+        """Device-resident G.711 ticks (indexing as push_device, 1-byte samples, any alignment)."""
+        check(self._lib.ewk_push_g711(self._h, C.c_void_p(ptr), int(stride), int(tick_stride), int(n_ticks),
+                                      _law(law), _lib.EWK_PUSH_DEVICE))
 
     def poll(self, cap: Optional[int] = None, lagged: bool = False) -> np.ndarray:
         """Drain queued events as a structured array (see _lib.EVENT_DTYPE).
@@ -537,11 +573,26 @@ class StreamEngine(Engine):
         self._push_streams(self._lib.ewk_push_streams_pcm16, streams, np.ascontiguousarray(pcm16, dtype=np.int16),
                            "pcm16")
 
+    def push_streams_g711(self, streams, codes: np.ndarray, law: str) -> None:
+        """push_streams with G.711 code bytes, uint8 [len(streams), n_ticks * input_block] (host),
+        all of `law` ("ulaw" or "alaw"); a fleet that mixes laws makes two calls, or uses
+        push_chunks_g711."""
+        law = _law(law)
+        self._push_streams(lambda *a: self._lib.ewk_push_streams_g711(*a[:-1], law, a[-1]), streams,
+                           np.ascontiguousarray(codes, dtype=np.uint8), "codes")
+
     def push_streams_device(self, streams, ptr: int, stride: int, tick_stride: int = 0, n_ticks: int = 1,
-                            pcm16: bool = False) -> None:
+                            pcm16: bool = False, g711: Optional[str] = None) -> None:
         """Device-resident ticks for a subset: row i, tick t at ptr + es * (i * stride + t * tick_stride)
-        (es = 4, or 2 with pcm16=True) goes to stream streams[i].  `streams` stays a host list."""
+        (es = 4, 2 with pcm16=True, or 1 with g711="ulaw" / "alaw") goes to stream streams[i].
+        `streams` stays a host list."""
         s = self._stream_list(streams)
+        if g711 is not None:
+            if pcm16:
+                raise ValueError("pcm16 and g711 exclude each other")
+            check(self._lib.ewk_push_streams_g711(self._h, _lib.i32ptr(s), s.size, C.c_void_p(ptr), int(stride),
+                                                  int(tick_stride), int(n_ticks), _law(g711), _lib.EWK_PUSH_DEVICE))
+            return
         fn = self._lib.ewk_push_streams_pcm16 if pcm16 else self._lib.ewk_push_streams
         check(fn(self._h, _lib.i32ptr(s), s.size, C.c_void_p(ptr), int(stride), int(tick_stride), int(n_ticks),
                  _lib.EWK_PUSH_DEVICE))
@@ -592,15 +643,44 @@ class StreamEngine(Engine):
         """push_chunks with int16 PCM chunks (decoded on the device; an int16 ring stores them as they are)."""
         self._push_chunks(self._lib.ewk_push_chunks_pcm16, streams, chunks, np.int16)
 
-    def push_chunks_device(self, streams, ptr: int, n_pcm: int, offsets, counts, pcm16: bool = False) -> None:
+    def _chunk_laws(self, law, n: int):
+        """(law, laws) of ewk_push_chunks_g711 from one name or a sequence with one name per chunk."""
+        if isinstance(law, str):
+            return _law(law), None
+        laws = np.array([_law(l) for l in law], np.uint8)
+        if laws.size != n:
+            raise ValueError(f"{n} streams listed, {laws.size} laws given")
+        return 0, laws
+
+    def push_chunks_g711(self, streams, chunks, law) -> None:
+        """push_chunks with G.711 code bytes (uint8 chunks of any length: an RTP client's 160-byte
+        packets as they arrive), decoded on the device.  `law` is "ulaw" or "alaw" for every chunk,
+        or a sequence with one name per chunk: a fleet mixes PCMU and PCMA in one call.  Needs an
+        input rate (set_input_rate(8000))."""
+        s = self._stream_list(streams)
+        one, laws = self._chunk_laws(law, s.size)
+        lp = laws.ctypes.data_as(C.c_void_p) if laws is not None else None
+        self._push_chunks(lambda *a: self._lib.ewk_push_chunks_g711(*a[:-1], one, lp, a[-1]), s, chunks, np.uint8)
+
+    def push_chunks_device(self, streams, ptr: int, n_pcm: int, offsets, counts, pcm16: bool = False,
+                           g711=None) -> None:
         """Device-resident chunks: chunk i is the counts[i] samples at ptr + es * offsets[i] (es = 4,
-        or 2 with pcm16=True) of a buffer of n_pcm samples; any offset, aligned or not.  `streams`,
-        `offsets` and `counts` stay host lists."""
+        2 with pcm16=True, or 1 with g711 = a law name or one name per chunk) of a buffer of n_pcm
+        samples; any offset, aligned or not.  `streams`, `offsets` and `counts` stay host lists."""
         s = self._stream_list(streams)
         o = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
         c = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
         if o.size != s.size or c.size != s.size:
             raise ValueError(f"{s.size} streams listed, {o.size} offsets and {c.size} counts given")
+        if g711 is not None:
+            if pcm16:
+                raise ValueError("pcm16 and g711 exclude each other")
+            one, laws = self._chunk_laws(g711, s.size)
+            check(self._lib.ewk_push_chunks_g711(self._h, _lib.i32ptr(s), s.size, C.c_void_p(ptr), int(n_pcm),
+                                                 _lib.i64ptr(o), _lib.i32ptr(c), one,
+                                                 laws.ctypes.data_as(C.c_void_p) if laws is not None else None,
+                                                 _lib.EWK_PUSH_DEVICE))
+            return
         fn = self._lib.ewk_push_chunks_pcm16 if pcm16 else self._lib.ewk_push_chunks
         check(fn(self._h, _lib.i32ptr(s), s.size, C.c_void_p(ptr), int(n_pcm), _lib.i64ptr(o), _lib.i32ptr(c),
                  _lib.EWK_PUSH_DEVICE))

@@ -180,7 +180,8 @@ class SoundBuffer:
     """The reference SoundBuffer protocol (wakeword.py:405-517) on a 1-stream
     GPU engine.  ``source`` replaces the PortAudio InputStream; ``pump()``
     delivers one callback block (what PortAudio does every 0.1 s); a source whose reads are not
-    ticks (ArraySource(read_sizes=), MicSource(blocksize=0)) is re-blocked on the device."""
+    ticks (ArraySource(read_sizes=), MicSource(blocksize=0)) is re-blocked on the device, and the
+    uint8 blocks of a source with a ``codec`` (G.711, ArraySource(codec=)) are decoded there."""
 
     FREQUENCY = FREQUENCY
     MIN_THRESHOLD = 0.005
@@ -198,17 +199,24 @@ class SoundBuffer:
         rate = int(getattr(source, "rate", FREQUENCY) or FREQUENCY)
         if rate != FREQUENCY:
             self.engine.set_input_rate(rate)
+        self._codec = getattr(source, "codec", None)   # "ulaw" / "alaw": the source's blocks are G.711 code bytes
         self._chunked = False   # a read of another length than a tick has gone through push_chunks
         self.source.start()
 
     def pump(self) -> np.ndarray:
         blk = self.source.read()
-        a = np.asarray(blk, np.float32).reshape(1, -1)
+        a = np.asarray(blk, np.float32 if self._codec is None else np.uint8).reshape(1, -1)
         # a tick goes through push as ever -- unless samples of an earlier packet are pending, which it must follow
         if a.shape[1] == self.engine.input_block and not (self._chunked and self.engine.stream_pending([0])[0]):
-            self.engine.push(a)
+            if self._codec is None:
+                self.engine.push(a)
+            else:
+                self.engine.push_g711(a, self._codec)
         else:   # a packet of another length than a tick: re-blocked on the device
-            self.engine.push_chunks([0], [a[0]])
+            if self._codec is None:
+                self.engine.push_chunks([0], [a[0]])
+            else:
+                self.engine.push_chunks_g711([0], [a[0]], self._codec)
             self._chunked = True
         return blk
 

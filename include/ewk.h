@@ -556,6 +556,49 @@ int ewk_compact_positives(ewk_engine* e, const double* d_score, const uint8_t* d
  * host arrays unless EWK_PCM_DEVICE (then both are device memory, asynchronous). */
 int ewk_decode_pcm16(ewk_engine* e, const int16_t* in, int64_t n, float* out, int32_t flags);
 
+/* ---- G.711 ingest: PCMU / PCMA decoded on the device ------------------------------ */
+/* The baseline RTP payloads are G.711 mu-law (PCMU) and A-law (PCMA): one code byte per sample at
+ * 8 kHz.  A code is a 16-bit integer v (csrc/ewk_g711.h: branch-free integer arithmetic, equal to
+ * CPython's audioop.ulaw2lin / alaw2lin at width 2 on all 256 codes; mu-law -32124..32124 with 0x7F
+ * and 0xFF both 0, A-law -32256..32256 with smallest magnitude 8), and the sample is v / 32768,
+ * exact in float32 and the expression every PCM16 decode of the engine uses: an engine pushed G.711
+ * bytes produces what an engine pushed the decoded PCM16 produces -- every event field, the
+ * score's bits, the ring samples and the thresholds.  The codec is memoryless: there is no
+ * per-stream state, resets, ewk_set_input_rate and snapshots are unchanged, and a stream may be
+ * pushed float32, PCM16 and G.711 in any order, tick by tick. */
+#define EWK_G711_ULAW 0
+#define EWK_G711_ALAW 1
+/* Host only, no engine, no device: the 256 decoded values of a law.  EWK_EINVAL for another law. */
+int ewk_g711_table(int32_t law, int16_t* out256);
+/* One-shot decode to float32, shaped like ewk_decode_pcm16: host arrays unless EWK_PCM_DEVICE
+ * (then both are device memory and the call is asynchronous); `in` at any byte alignment.  Works
+ * on an engine without streams. */
+int ewk_decode_g711(ewk_engine* e, const uint8_t* in, int64_t n, float* out, int32_t law, int32_t flags);
+/* Ticks for every stream: the arguments of ewk_push_many_pcm16, the samples one byte each.
+ * Strides, offsets and counts are in samples, which are bytes here; any byte alignment of pcm is
+ * legal, for host and device pointers, and a stride or tick_stride need not be a multiple of 4.
+ * G.711 is an 8 kHz codec and the gate runs at cfg.sample_rate, so an input rate must be set
+ * (ewk_set_input_rate, normally 8000; any rate the resampler accepts works, the bytes are just
+ * samples): without one the push returns EWK_EINVAL and says so.  An EWK_RING_I16 ring, which
+ * refuses an input rate, refuses G.711 too.  A law outside {0, 1} is EWK_EINVAL.  Everything else
+ * is as for PCM16: the list rules of ewk_push_streams, the refusal of a tick push onto pending
+ * samples, desynchronisation, ewk_stream_ticks, gate launches cut and scored as for
+ * ewk_push_many.  The codes are decoded inside the resampler launch (profile kind 3), read once,
+ * straight into its LDS staging; the gate kernels are those of a float32 push with a rate set.
+ * Every rule is validated on the host before anything is enqueued or changed. */
+int ewk_push_g711(ewk_engine* e, const uint8_t* pcm, int64_t stride, int64_t tick_stride,
+                  int32_t n_ticks, int32_t law, int32_t flags);
+int ewk_push_streams_g711(ewk_engine* e, const int32_t* streams, int32_t n, const uint8_t* pcm,
+                          int64_t stride, int64_t tick_stride, int32_t n_ticks, int32_t law, int32_t flags);
+/* Packet ingest (ewk_push_chunks_pcm16's arguments and rules): an RTP client's 160-byte packets
+ * as they arrive.  laws: NULL (every chunk is `law`) or a host array [n], one law per chunk -- a
+ * fleet mixes PCMU and PCMA in one call; an entry outside {0, 1} is EWK_EINVAL naming it (`law` is
+ * not read then).  The codes are decoded by the assembly launch (profile kind 4) into the float32
+ * carry and tick rows; ewk_stream_pending counts samples as before. */
+int ewk_push_chunks_g711(ewk_engine* e, const int32_t* streams, int32_t n, const uint8_t* pcm, int64_t n_pcm,
+                         const int64_t* offsets, const int32_t* counts, int32_t law, const uint8_t* laws,
+                         int32_t flags);
+
 /* ---- ingest at the source's own sample rate: the device resampler ------------------ */
 /* The reference gets 16 kHz from PortAudio (sd.InputStream(samplerate=16000), wakeword.py:438-444)
  * and from librosa.load(sr=16000); sources without either (network, files, decoders whose output

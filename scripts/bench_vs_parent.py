@@ -5,17 +5,20 @@
          table or list: tick_ms_median and gate_ms_per_launch), and
   bench  bench.py --gpus 1 --steps 20 --warmup 5 (`value`), and
   chunks scripts/bench_push_chunks.py --cases cd (packet ingest at 8,192 streams: step_ms_median of
-         case c, one block per stream and push, and of case d, five 320-sample packets per tick),
+         case c, one block per stream and push, and of case d, five 320-sample packets per tick), and
+  resample scripts/bench_resample.py --cases bcd --rounds 3 --ticks 30 (the tick with an input rate
+         set, 48 kHz float32, 44.1 kHz float32 and 48 kHz PCM16: tick_ms_median and the resample stage
+         from ewk_profile_read kind 3),
 
 each in a fresh process per tree and round, the order of the two trees swapped every round.
 Acceptance as profiles/engine_split_vs_parent.json: this checkout's median inside the min..max of
 the parent's rounds.  A step that fails or runs past its time limit ends the script at once.
 
-    python scripts/bench_vs_parent.py --parent DIR [--what tick,bench,chunks] [--rounds 5] --out FILE
+    python scripts/bench_vs_parent.py --parent DIR [--what tick,bench,chunks,resample] [--rounds 5] --out FILE
 
 DIR holds the parent commit with its own libewk.so built in place (git worktree + python -m
-easywakeword_amd.build there).  An existing FILE is extended: `tick`, `bench` and `chunks` may
-come from separate calls.
+easywakeword_amd.build there).  An existing FILE is extended: `tick`, `bench`, `chunks` and
+`resample` may come from separate calls.  FILE is rewritten after every round.
 """
 import argparse
 import json
@@ -69,6 +72,13 @@ def main():
     if "chunks" in what:
         for t in trees:
             res[t]["chunk_c_ms"], res[t]["chunk_d_ms"] = [], []
+    rs_rows = {"b": "rs48_f32", "c": "rs441_f32", "d": "rs48_pcm16"}
+    if "resample" in what:
+        for t in trees:
+            for v in rs_rows.values():
+                res[t][v + "_tick_ms"], res[t][v + "_stage_ms"] = [], []
+    names = ("tick_ms", "gate_ms", "bench_value", "chunk_c_ms", "chunk_d_ms") + tuple(
+        v + s for v in rs_rows.values() for s in ("_tick_ms", "_stage_ms"))
     for r in range(args.rounds):
         order = ["parent", "new"] if r % 2 == 0 else ["new", "parent"]
         for t in order:
@@ -83,8 +93,20 @@ def main():
                 d = run_json(trees[t], ["scripts/bench_push_chunks.py", "--cases", "cd"], 240)
                 res[t]["chunk_c_ms"].append(d["step"]["c"]["step_ms_median"])
                 res[t]["chunk_d_ms"].append(d["step"]["d"]["step_ms_median"])
+            if "resample" in what:
+                d = run_json(trees[t], ["scripts/bench_resample.py", "--cases", "bcd", "--rounds", "3", "--ticks", "30"],
+                             300)
+                for k, v in rs_rows.items():
+                    res[t][v + "_tick_ms"].append(d["tick"][k]["tick_ms_median"])
+                    res[t][v + "_stage_ms"].append(d["profile"][k]["resample_ms_per_tick"])
             print(f"round {r} {t} done", flush=True)
-    names = ("tick_ms", "gate_ms", "bench_value", "chunk_c_ms", "chunk_d_ms")
+        summarise(res, trees, names)
+        res["rounds_done"] = r + 1
+        write(args.out, res)
+    print(json.dumps(res))
+
+
+def summarise(res, trees, names):
     for t in trees:
         for name in names:
             if res[t].get(name):
@@ -99,11 +121,15 @@ def main():
                    "(scripts/bench_push_chunks.py --cases cd, step_ms_median of cases c and d): the parent "
                    "commit's build against this one, a fresh process per tree and round, the order swapped every "
                    "round (scripts/bench_vs_parent.py); acceptance: the new build's median inside the min..max of "
-                   "the parent's rounds")
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
+                   "the parent's rounds; rs*_tick_ms / rs*_stage_ms: the tick and the resample stage (kind 3) of "
+                   "scripts/bench_resample.py --cases bcd --rounds 3 --ticks 30 at 48 kHz float32, 44.1 kHz float32 "
+                   "and 48 kHz PCM16")
+
+
+def write(out, res):
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
         f.write(json.dumps(res) + "\n")
-    print(json.dumps(res))
 
 
 if __name__ == "__main__":
