@@ -290,11 +290,7 @@ __device__ __forceinline__ void rs_frames(const double2 (&xw)[NF][4], const bool
         for (int r = 0; r < 4; ++r) x[j][r] = xw[j][r];
     // radix-4 Stockham autosort: v[r] = d[j + 64 r], v[r] *= W_{4 Ns}^{r (j % Ns)}, DFT4,
     // V[r] -> d'[(j / Ns) 4 Ns + j % Ns + r Ns]; natural order after Ns = 64
-#ifndef EWK_RS_SKIP_FFT
     for (int it = 0; it < 4; ++it) {
-#else
-    for (int it = 0; it < 4; it += 3) {
-#endif
 #pragma unroll
         for (int j = 0; j < NF; ++j) {
             double2* buf = reinterpret_cast<double2*>(wbuf + RS_BUF) + 256 * j;
@@ -383,21 +379,13 @@ __device__ __forceinline__ void rs_frames(const double2 (&xw)[NF][4], const bool
 #pragma unroll
             for (int q = 0; q < kRsMelW; ++q) pw[q] = q < kw ? P[lo + q] : 0.0;   // lo + q < 2 * 256: inside the frame's buffer
             double acc = 0.0;
-#ifndef EWK_RS_SKIP_MEL
             // past the band: weight 0 times a finite power of this frame (its FFT buffer; a NaN
             // there means NaN samples, and then every bin is NaN) adds +-0, and acc + -0 = acc
 #pragma unroll
             for (int q = 0; q < kRsMelW; ++q)
                 if (q < kw) acc = fma((double)ww[q], pw[q], acc);
-#else   // (timing experiment: one bin per band)
-            acc = pw[0] + (double)ww[0] + (double)nw;
-#endif
-#ifndef EWK_RS_SKIP_LOG
             // (ewk_db64.h: 10 log10 in ~30 float64 instructions; the library's log10 takes ~100)
             const double db = ewk_db64(acc < 1e-10 ? 1e-10 : acc);   // np.maximum: NaN propagates
-#else
-            const double db = acc;
-#endif
             // the A operand, or -0.0 for a value the clamp replaces (NaN included): fma(d, -0, A) = A
             // as with +0, and db is never -0.0 (10 log10(acc), acc >= 1e-10), so -0.0 also marks
             // the B operand for rs_dct (no second tile)
@@ -434,11 +422,7 @@ __device__ __forceinline__ void rs_dct(const unsigned char* smem, unsigned char*
     if (lane < 60) {
         const int k = lane % NMFCC, h = lane / NMFCC;
         const int m0 = 43 * h;
-#ifndef EWK_RS_SKIP_DCT
         const int m1 = min(NMEL, m0 + 43);
-#else
-        const int m1 = m0 + 1;
-#endif
         const double* dp = D + k;
         const double4* xp = reinterpret_cast<const double4*>(xa);
         // one band: A[f] += D[k][m] x[m][f]; B[f] += D[k][m] where x[m][f] was clamped (-0.0)

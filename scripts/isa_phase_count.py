@@ -3,7 +3,8 @@
     python scripts/isa_phase_count.py [--kernel k_score_f32ILi0ELi0E] [--json out.json]
 
 Compiles csrc/ewk_mfcc.hip to gfx950 assembly with line tables, attributes every instruction
-of the kernel to the source line its .loc names, groups the lines into phases (the frame
+of the kernel to the source line its .loc names (in ewk_mfcc.hip or one of its stage headers,
+ewk_mfcc_*.h: a per-file table of function ranges), groups the lines into phases (the frame
 pass's stages, the tile work, the segment work) and counts VALU (v_*, MFMA apart), LDS (ds_*),
 VMEM (buffer_/global_), SALU (s_*) instructions per phase and per inlined instance.
 
@@ -25,13 +26,44 @@ import sys
 from collections import defaultdict
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "easywakeword_amd", "csrc", "ewk_mfcc.hip")
+CSRC = os.path.join(ROOT, "easywakeword_amd", "csrc")
+SRC = os.path.join(CSRC, "ewk_mfcc.hip")
+# the scorer's own files: the translation unit and its stage headers (function names are unique
+# across them); frame_pass and its phase comments live in FRAME_PASS_FILE
+OWN_FILES = ("ewk_mfcc.hip", "ewk_mfcc_layout.h", "ewk_mfcc_dft.h", "ewk_mfcc_tile.h", "ewk_mfcc_fft.h",
+             "ewk_mfcc_dct.h", "ewk_mfcc_stats.h")
+FRAME_PASS_FILE = "ewk_mfcc_fft.h"
+# function -> phase
+PHASES = (("stage_load", "pass: staging"), ("stage_store", "pass: staging"),
+          ("dft4", "pass: fft helper"), ("dft16_stage2", "pass: fft helper"), ("dft16_perm", "pass: fft helper"),
+          ("dft16_perm_win", "pass: fft helper"), ("cmul", "pass: fft helper"), ("xpose_write", "pass: transpose"),
+          ("split2", "pass: tilewrite"), ("split8", "pass: tilewrite"), ("f16_trunc", "tile: clamp"),
+          ("clamp_load", "tile: clamp"), ("clamp_store", "tile: clamp"), ("tile_dct", "tile: dct"),
+          ("stats_add", "tile: stats"), ("stats_replace", "recompute: stats"), ("wave_min", "tile: wave min/max"),
+          ("wave_max", "tile: wave min/max"), ("zero_rows", "tile: zero rows"),
+          ("finish_stats", "segment: finish_stats"), ("row_sum_d", "segment: finish_stats"),
+          ("wave_sum_d", "segment: epilogue"), ("score_epilogue", "segment: epilogue"),
+          ("score_f64_finish", "segment: epilogue"), ("score_f32_finish", "segment: epilogue"),
+          ("tile_passes", "recompute: tile_passes"), ("fix_tile", "recompute: fix_tile"),
+          ("segment_stats", "segment: segment_stats body"), ("work_claim", "segment: work claim"),
+          ("work_order", "segment: work claim"), ("work_describe", "segment: work claim"),
+          ("make_src", "segment: work claim"), ("k_score_f32", "kernel: setup / loop"),
+          # functions that used to fall through to `line N` rows; phases of their own, so the rows
+          # above count what they always counted
+          ("lds_order", "kernel: lds_order"), ("f16_lo", "tile: clamp (f16 unpack)"), ("f16_hi", "tile: clamp (f16 unpack)"),
+          ("tile_chunk", "pass: tilewrite (tile_chunk)"),
+          ("pair_sum_lo", "tile: clamp mask"), ("pair_sum_hi", "tile: clamp mask"), ("clamp_pair", "tile: clamp mask"),
+          ("clamp_mask", "tile: clamp mask"), ("tile_dct_m", "tile: dct"),
+          ("shift_tile_add", "tile: shift sums"), ("shift_apply", "tile: shift sums"),
+          ("stats_replace_shift", "recompute: shift stats"), ("pass_mins", "tile: pass minima"),
+          ("dpp_d", "segment: row sums (dpp_d)"), ("wave_sum_f", "segment: scout"),
+          ("scout_batch", "segment: scout"), ("scout_tiles", "segment: scout"))
 
 
 def func_ranges(src_lines):
-    """{function name: (first line, last line)} of the device functions in ewk_mfcc.hip."""
+    """{function name: [(first line, last line)]} of the device functions in one source file."""
     out = {}
-    pat = re.compile(r"^(?:template <[^>]*>\s*)?__(?:device|global)__.*?\b(\w+)\s*\(")
+    pat = re.compile(r"^(?:template <[^>]*>\s*)?__(?:device|global)__ (?:__launch_bounds__\([^)]*\) )?.*?\b(\w+)\s*\(")
     starts = []
     for i, l in enumerate(src_lines, 1):
         m = pat.match(l)
@@ -82,55 +114,43 @@ def main():
                     "--cuda-device-only", "-S", "-gline-tables-only", SRC, "-o", out_s], check=True,
                    capture_output=True)
     s = open(out_s).read()
-    src = open(SRC).read().split("\n")
-    fr = func_ranges(src)
-    mk = markers(src)
-    fp_lo, fp_hi = fr["frame_pass"][0]
+    fr = {}   # file name -> its function ranges
+    for name in OWN_FILES:
+        src = open(os.path.join(CSRC, name)).read().split("\n")
+        fr[name] = func_ranges(src)
+        if name == FRAME_PASS_FILE:
+            mk = markers(src)
+    fp_lo, fp_hi = fr[FRAME_PASS_FILE]["frame_pass"][0]
     # frame-pass sub-phases by the marker comments
     cuts = sorted(mk.items(), key=lambda kv: kv[1])
 
-    own = {int(m.group(1)) for m in re.finditer(r'^\s*\.file\s+(\d+)\s+"[^"]*"\s+"([^"]*)"', s, re.M)
-           if m.group(2).endswith("ewk_mfcc.hip")}
-    rescore = {int(m.group(1)) for m in re.finditer(r'^\s*\.file\s+(\d+)\s+"[^"]*"\s+"([^"]*)"', s, re.M)
-               if m.group(2).endswith(("ewk_rescore.h", "ewk_db64.h"))}
+    files = {int(m.group(1)): os.path.basename(m.group(2))
+             for m in re.finditer(r'^\s*\.file\s+(\d+)\s+"[^"]*"\s+"([^"]*)"', s, re.M)}
+    own = {n: f for n, f in files.items() if f in OWN_FILES}
+    rescore = {n for n, f in files.items() if f in ("ewk_rescore.h", "ewk_db64.h")}
     last = ["kernel: setup / loop"]
 
     def phase_of(file_no, line):
         if file_no in rescore:
             return "segment: epilogue (fp64 listing)"
-        if file_no not in own:   # HIP / math headers: the caller's phase
+        if file_no not in own:   # HIP / math headers, shared project headers: the caller's phase
             return last[0]
-        last[0] = own_phase(line)
+        last[0] = own_phase(own[file_no], line)
         return last[0]
 
-    def own_phase(line):
-        if fp_lo <= line <= fp_hi:
-            name = "pass: setup"
+    def own_phase(name, line):
+        if name == FRAME_PASS_FILE and fp_lo <= line <= fp_hi:
+            ph = "pass: setup"
             for k, l0 in cuts:
                 if line >= l0:
-                    name = "pass: " + k
-            return name
-        for f in ("stage_load", "stage_store"):
-            for lo, hi in fr.get(f, []):
-                if lo <= line <= hi:
-                    return "pass: staging"
-        for f, ph in (("dft4", "pass: fft helper"), ("dft16_stage2", "pass: fft helper"), ("dft16_perm", "pass: fft helper"),
-                      ("dft16_perm_win", "pass: fft helper"), ("cmul", "pass: fft helper"), ("xpose_write", "pass: transpose"),
-                      ("split2", "pass: tilewrite"), ("split8", "pass: tilewrite"), ("f16_trunc", "tile: clamp"),
-                      ("clamp_load", "tile: clamp"), ("clamp_store", "tile: clamp"), ("tile_dct", "tile: dct"),
-                      ("stats_add", "tile: stats"), ("stats_replace", "recompute: stats"), ("wave_min", "tile: wave min/max"),
-                      ("wave_max", "tile: wave min/max"), ("zero_rows", "tile: zero rows"),
-                      ("finish_stats", "segment: finish_stats"), ("row_sum_d", "segment: finish_stats"),
-                      ("wave_sum_d", "segment: epilogue"), ("score_epilogue", "segment: epilogue"),
-                      ("score_f64_finish", "segment: epilogue"), ("score_f32_finish", "segment: epilogue"),
-                      ("tile_passes", "recompute: tile_passes"), ("fix_tile", "recompute: fix_tile"),
-                      ("segment_stats", "segment: segment_stats body"), ("work_claim", "segment: work claim"),
-                      ("work_order", "segment: work claim"), ("work_describe", "segment: work claim"),
-                      ("make_src", "segment: work claim"), ("k_score_f32", "kernel: setup / loop")):
-            for lo, hi in fr.get(f, []):
+                    ph = "pass: " + k
+            return ph
+        for f, ph in PHASES:
+            for lo, hi in fr[name].get(f, []):
                 if lo <= line <= hi:
                     return ph
-        return f"line {line}"
+        # (line 0: compiler-generated code without a source line, whichever file it is charged to)
+        return f"line {line}" if line == 0 or name == "ewk_mfcc.hip" else f"{name} line {line}"
 
     names = [m for m in re.findall(r"^\s*\.type\s+(\S+),@function", s, re.M) if args.kernel in m]
     if not names:

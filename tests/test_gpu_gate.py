@@ -133,24 +133,6 @@ def test_many_streams_vs_oracle(template):
                 back = eng.read_segment(g[0], g[3], g[1])
                 b["ring_back_linear_score"] = float(lin.score([back], candidate_dtype="float64")[2][0])
         lin.close()
-        from easywakeword_amd import _lib
-        lib = _lib.load()
-        if hasattr(lib, "ewk_debug_coop"):   # -DEWK_COOP_DEBUG builds: what each wave of the scorer saw
-            ev = np.zeros((8192, 8, 4), np.int32)
-            th = np.zeros((8192, 8, 4), np.float32)
-            pd = np.zeros((8192, 8, 60), np.float64)
-            ms = np.zeros((8192, 40), np.float32)
-            import ctypes
-            vp = lambda a: ctypes.c_void_p(a.ctypes.data)   # (a bare int would pass as a 32-bit C int)
-            if lib.ewk_debug_coop(vp(ev), vp(th), vp(pd), vp(ms)) == 0:
-                for b in bad:
-                    g = b["mine"]
-                    key = (g[0] & 31) * 256 + (g[2] & 255)
-                    b["coop"] = dict(ev=ev[key], th=th[key], pd=pd[key], ms=ms[key])
-                    if key < 1024 and hasattr(lib, "ewk_debug_coop_tile"):
-                        tl = np.zeros((8, 512, 4), np.uint32)
-                        if lib.ewk_debug_coop_tile(ctypes.c_int(key), vp(tl)) == 0:
-                            b["coop"]["tile"] = tl
         path = dump("many_streams", dict(bad=bad, events=got))
         pytest.fail(f"{len(bad)} mismatches (evidence {path}): {bad[:4]}")
     assert n_ev > 20
