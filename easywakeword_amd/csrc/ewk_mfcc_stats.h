@@ -86,32 +86,48 @@ __device__ __forceinline__ void pass_mins(float x, float (&pm)[2]) {
     }
 }
 
-// Wave minimum of a float, no LDS: DPP row scan, then the four row results via readlane.
+// Wave minimum / maximum of a float, no LDS: a DPP row scan (row_shr 1, 2, 4, 8: lane 15 of a
+// row holds the row's), row_bcast:15 into rows 1 and 3 and row_bcast:31 into rows 2 and 3 (lane
+// 63 holds the wave's), one readlane.  Written out: through fminf / fmaxf every DPP step costs a
+// copy and a canonicalising v_max_f32 x, x beside the move and the min (ewk_mfcc_dct.h,
+// clamp_mask).  The hazard recogniser does not see into the statement, so it carries its own wait
+// states: s_nop 1 between a VALU write and a DPP read of the same register (two), s_nop 4 in
+// front (five: a VALU write of EXEC before a DPP instruction), s_nop 1 at the end for the
+// readlane.  A lane whose source is outside its row, or whose row the row_mask leaves out, keeps
+// its value.  A NaN operand yields the other operand (v_min_f32 / v_max_f32, IEEE mode), like
+// fminf / fmaxf; the callers' values (pass minima, the running max, scout energies) hold none.
+#define EWK_WAVE_RED(op)                                                                       \
+    "s_nop 4\n\t" op " %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"                    \
+    "s_nop 1\n\t" op " %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"                    \
+    "s_nop 1\n\t" op " %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"                    \
+    "s_nop 1\n\t" op " %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"                    \
+    "s_nop 1\n\t" op " %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"                 \
+    "s_nop 1\n\t" op " %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"                 \
+    "s_nop 1"
 __device__ __forceinline__ float wave_min(float x) {
-    x = fminf(x, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(x), __float_as_int(x), 0x111, 0xf, 0xf, false)));
-    x = fminf(x, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(x), __float_as_int(x), 0x112, 0xf, 0xf, false)));
-    x = fminf(x, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(x), __float_as_int(x), 0x114, 0xf, 0xf, false)));
-    x = fminf(x, __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(x), __float_as_int(x), 0x118, 0xf, 0xf, false)));
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 15));
-    const float r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 31));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 47));
-    const float r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
-    return fminf(fminf(r0, r1), fminf(r2, r3));
+    asm(EWK_WAVE_RED("v_min_f32_dpp") : "+v"(x));
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
+}
+__device__ __forceinline__ float wave_max(float x) {
+    asm(EWK_WAVE_RED("v_max_f32_dpp") : "+v"(x));
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
 }
 
 // Sum over the 16 lanes of each row (DPP row_shr scan, no LDS); the total lands in lane 15 of the row.
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double x) {   // DPP move of a double; lanes without a source read 0
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, 0xf, 0xf, false);
+// DPP move of a double: two dword moves.  BOUND: lanes without a source read 0 (the bound-control
+// form: no `old` register of zeros per half); the permutations below have a source in every lane.
+template <int CTRL, bool BOUND>
+__device__ __forceinline__ double dpp_d(double x) {
+    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(x), CTRL, 0xf, 0xf, BOUND);
+    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(x), CTRL, 0xf, 0xf, BOUND);
     return __hiloint2double(hi, lo);
 }
 
 __device__ __forceinline__ double row_sum_d(double x) {
-    x += dpp_d<0x111>(x);   // row_shr:1
-    x += dpp_d<0x112>(x);   // row_shr:2
-    x += dpp_d<0x114>(x);   // row_shr:4
-    x += dpp_d<0x118>(x);   // row_shr:8
+    x += dpp_d<0x111, true>(x);   // row_shr:1
+    x += dpp_d<0x112, true>(x);   // row_shr:2
+    x += dpp_d<0x114, true>(x);   // row_shr:4
+    x += dpp_d<0x118, true>(x);   // row_shr:8
     return x;
 }
 
@@ -126,42 +142,88 @@ __device__ __forceinline__ double wave_sum_d(double x) {
     return t;
 }
 
-// Sum of a float over the wave (DPP row scans, the row totals via readlane); uniform result.
-__device__ __forceinline__ float wave_sum_f(float x) {
+// Row scan of a float (row_shr 1, 2, 4, 8; lanes without a source add 0): lane 15 of a row holds
+// ((x0 + x1) + (x2 + x3)) + ... over the row's 16 lanes, a balanced tree.
+__device__ __forceinline__ float row_sum_f(float x) {
     x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x111, 0xf, 0xf, false));
     x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x112, 0xf, 0xf, false));
     x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x114, 0xf, 0xf, false));
     x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x118, 0xf, 0xf, false));
+    return x;
+}
+
+// Sum of a float over the wave (DPP row scans, the row totals via readlane); uniform result.
+__device__ __forceinline__ float wave_sum_f(float x) {
+    x = row_sum_f(x);
     return (__int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 15)) +
             __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 31))) +
            (__int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 47)) +
             __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63)));
 }
 
-// Wave maximum of a float (see wave_min).
-__device__ __forceinline__ float wave_max(float x) { return -wave_min(-x); }
+// The per-lane sums s1[0..4], s2[0..4] summed over the 16 frame columns of each row and handed
+// over, with cref, to the wave's scratch `pd` ([coefficient][S1, S2, cref] doubles; coefficient
+// 4 h + r for slot r < 4 of row h, 16 + h for slot 4).  Every total is the balanced tree of the
+// row_shr scan, ((x0 + x1) + (x2 + x3)) + ..., the same pairs added at every level (an addition
+// is commutative, so the pairing fixes the bits), but as a narrowing reduction: at each level the
+// two lanes of a pair exchange half of what they carry and each adds the other half, so a lane
+// carries 10, 5, 3, 2 and at last 1 value instead of 10 at all four levels (12 additions of
+// doubles, not 40).  Level by level, a lane's partner and what decides which half it keeps
+// (b0..b3: the bits of its column):
+//   columns 2i | 2i+1        partner col ^ 1  (quad_perm [1,0,3,2])   k1 = b0 ^ b2: keeps s2, else s1
+//   pairs of a quad          partner col ^ 2  (quad_perm [2,3,0,1])   k2 = b1 ^ b2: the odd slot
+//   quads of a half row      partner col ^ 7  (row_half_mirror)       k3 = b2 ^ b3: slots 2, 3
+//   half rows                partner col ^ 15 (row_mirror)            both lanes add
+// A partner at any level holds the same kind of value (k1 is the same in col ^ 2, col ^ 7 and
+// col ^ 15, k2 in col ^ 7 and col ^ 15, k3 in col ^ 15).  Slot 4 has no partner slot after the
+// first level and is added over the full butterfly.  In the end a lane holds the total of
+// (k1 ? s2 : s1)[2 k3 + k2] and of (k1 ? s2 : s1)[4] and stores both; lanes that hold the same
+// total store the same bits.
+__device__ __forceinline__ void row_sums_to_pd(const float (&cref)[kSlots], const double (&s1)[kSlots],
+                                               const double (&s2)[kSlots], int lane, double* pd) {
+    // (once per segment: the lane's predicates and addresses are recomputed here, not kept in
+    // registers across the work loop and its frame passes)
+    asm volatile("" : "+v"(lane));
+    const int col = lane & 15, h = lane >> 4;
+    const bool k1 = ((col ^ (col >> 2)) & 1) != 0, k2 = (((col >> 1) ^ (col >> 2)) & 1) != 0,
+               k3 = (((col >> 2) ^ (col >> 3)) & 1) != 0;
+    double v[kSlots];
+#pragma unroll
+    for (int i = 0; i < kSlots; ++i) {   // columns 2i, 2i + 1
+        const double a = s1[i], b = s2[i];
+        v[i] = (k1 ? b : a) + dpp_d<0xB1, false>(k1 ? a : b);
+    }
+    double w[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {        // the two pairs of a quad
+        const double a = v[2 * i], b = v[2 * i + 1];
+        w[i] = (k2 ? b : a) + dpp_d<0x4E, false>(k2 ? a : b);
+    }
+    v[4] += dpp_d<0x4E, false>(v[4]);
+    const double w0 = w[0], w1 = w[1];
+    double z = (k3 ? w1 : w0) + dpp_d<0x141, false>(k3 ? w0 : w1);   // the two quads of a half row
+    v[4] += dpp_d<0x141, false>(v[4]);
+    z += dpp_d<0x140, false>(z);       // the two half rows
+    v[4] += dpp_d<0x140, false>(v[4]);
+    // (selects of values: a conditional between the array's elements becomes an indexed read of
+    // cref, which puts the array in scratch memory)
+    const float r0 = cref[0], r1 = cref[1], r2 = cref[2], r3 = cref[3];
+    const float c01 = k2 ? r1 : r0, c23 = k2 ? r3 : r2;
+    const float cz = k3 ? c23 : c01;
+    const int k = 4 * h + 2 * (int)k3 + (int)k2, kk = 16 + h;
+    pd[3 * k + (int)k1] = z;
+    pd[3 * k + 2] = (double)cz;
+    pd[3 * kk + (int)k1] = v[4];
+    pd[3 * kk + 2] = (double)cref[4];
+}
 
-// Reduce the per-lane sums over the 16 frame columns (DPP, totals in lane 15 of each
-// row), hand each coefficient's (S1, S2, cref) to lane k = coefficient through the
+// Reduce the per-lane sums over the 16 frame columns (row_sums_to_pd), hand each
+// coefficient's (S1, S2, cref) to lane k = coefficient through the
 // wave's scratch `pd` (20 x 3 doubles), and finish there: lane k < 20 returns its mean in
 // s1[0] and its population std in s2[0] (one fp64 division + sqrt per lane, not eight).
 __device__ __forceinline__ void finish_stats(int T, const float (&cref)[kSlots], double (&s1)[kSlots], double (&s2)[kSlots],
                                              int lane, double* pd) {
-#pragma unroll
-    for (int i = 0; i < kSlots; ++i) {
-        s1[i] = row_sum_d(s1[i]);
-        s2[i] = row_sum_d(s2[i]);
-    }
-    if ((lane & 15) == 15) {
-        const int h = lane >> 4;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int k = 4 * h + r;
-            pd[3 * k] = s1[r]; pd[3 * k + 1] = s2[r]; pd[3 * k + 2] = (double)cref[r];
-        }
-        const int k2 = 16 + h;   // slot 4 of row h: coefficient 16 + h
-        pd[3 * k2] = s1[4]; pd[3 * k2 + 1] = s2[4]; pd[3 * k2 + 2] = (double)cref[4];
-    }
+    row_sums_to_pd(cref, s1, s2, lane, pd);
     lds_order();
     if (lane < NMFCC) {
         const double S1 = pd[3 * lane], S2 = pd[3 * lane + 1], r0 = pd[3 * lane + 2];
@@ -290,10 +352,53 @@ __device__ __forceinline__ void scout_batch(const SegSrc<RING>& v, int t0, int l
     }
 }
 
+// The same sums for a linear batch, sixteen lanes per tile: lane l of lane row R loads columns
+// 4l .. 4l + 3 of each of the four sample rows of tile t0 + 4g + R (one 16-byte load per sample
+// row: four loads serve four tiles; the range check zeroes each dword past the segment end on its
+// own, scripts/probes/buffer_range_probe.hip, so a row that straddles the end reads what four
+// dword loads read).  Each column's square sum is the chain above; (c0 + c1) + (c2 + c3) in the
+// lane and the row scan's distances 1 and 2 are the four levels of wave_sum_f's tree over 16
+// consecutive columns, its distances 4 and 8 are (r0 + r1) + (r2 + r3): the same pairs at every
+// level, so the same bits.  The tile's total lands in lane 15 of its lane row.  (Lanes t0 ..
+// t0 + 4G - 1 are set, past ntile to the 0 of samples past the end, where scout_batch leaves
+// -1 beyond its batch: such lanes are neither ranked nor near, and never the maximum.)
+template <int G>
+__device__ __forceinline__ void scout_quads(const SegSrc<0>& v, int t0, int lane, float& e) {
+    int ln = lane;   // (the load offsets are recomputed per call, not kept across the work loop)
+    asm volatile("" : "+v"(ln));
+    const int R = ln >> 4, l = ln & 15;
+    floatx4 x[G][4];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int qs = (t0 + 4 * g + R) * 16 * HOP + 640 * q + 64 + 4 * l;
+            x[g][q] = __builtin_bit_cast(floatx4, __builtin_amdgcn_raw_buffer_load_b128(v.rsrc, qs * 4, 0, 0));
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        float c[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            c[i] = x[g][0][i] * x[g][0][i];
+#pragma unroll
+            for (int q = 1; q < 4; ++q) c[i] = fmaf(x[g][q][i], x[g][q][i], c[i]);
+        }
+        const float tot = row_sum_f((c[0] + c[1]) + (c[2] + c[3]));
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float tr = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(tot), 16 * r + 15));
+            if (lane == t0 + 4 * g + r) e = tr;
+        }
+    }
+}
+
 // Scout of a segment's tiles (tile t: frames 16t .. 16t + 15): the energy of 4 x 64 of its
 // samples (one 64-sample row every 640), wave-reduced; lane t returns the estimate for tile
 // t (t < ntile <= 64).  Only a processing-order heuristic: the results do not depend on it.
 // The loads of 8 tiles are in flight together (one memory round trip per 1.3 s of segment).
+// Linear batches take scout_quads; the rings (wrap, int16 samples) keep one lane per column.
 // (scripts/scout_sim.py replays the order on the oracle's log-mel: this scout leaves ~7 % of
 // the bench's tiles to recompute, none with the true tile maxima; max-of-rows variants and
 // twice the loads reach 6.1 %.)
@@ -304,7 +409,10 @@ __device__ __forceinline__ float scout_tiles(const SegSrc<RING>& v, int ntile, i
         // the batch sized to the tiles left (a short segment's scout issues 2 or 4 tiles' loads
         // and reductions, not 8)
         const int left = ntile - t0;
-        if (left <= 2) scout_batch<RING, 2>(v, t0, lane, e);
+        if constexpr (RING == 0) {
+            if (left <= 4) scout_quads<1>(v, t0, lane, e);
+            else scout_quads<kScoutBatch / 4>(v, t0, lane, e);
+        } else if (left <= 2) scout_batch<RING, 2>(v, t0, lane, e);
         else if (left <= 4) scout_batch<RING, 4>(v, t0, lane, e);
         else scout_batch<RING, kScoutBatch>(v, t0, lane, e);
     }
@@ -674,18 +782,7 @@ __device__ void segment_stats_coop(const SegSrc<RING>& v, unsigned char* smem, f
     }
     // this wave's per-coefficient (s1, s2, cref) -> its scratch, as doubles [coef][3]
     double* pd = reinterpret_cast<double*>(scr);
-#pragma unroll
-    for (int i = 0; i < kSlots; ++i) { s1[i] = row_sum_d(s1[i]); s2[i] = row_sum_d(s2[i]); }
-    if (col == 15) {
-        const int h = lane >> 4;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int k = 4 * h + r;
-            pd[3 * k] = s1[r]; pd[3 * k + 1] = s2[r]; pd[3 * k + 2] = (double)cref[r];
-        }
-        const int k2 = 16 + h;   // slot 4 of row h: coefficient 16 + h
-        pd[3 * k2] = s1[4]; pd[3 * k2 + 1] = s2[4]; pd[3 * k2 + 2] = (double)cref[4];
-    }
+    row_sums_to_pd(cref, s1, s2, lane, pd);
     __syncthreads();
     if (wave == 0) {
         double mean = 0.0, sd = 0.0;

@@ -57,7 +57,9 @@ PHASES = (("stage_load", "pass: staging"), ("stage_store", "pass: staging"),
           ("shift_tile_add", "tile: shift sums"), ("shift_apply", "tile: shift sums"),
           ("stats_replace_shift", "recompute: shift stats"), ("pass_mins", "tile: pass minima"),
           ("dpp_d", "segment: row sums (dpp_d)"), ("wave_sum_f", "segment: scout"),
-          ("scout_batch", "segment: scout"), ("scout_tiles", "segment: scout"))
+          ("scout_batch", "segment: scout"), ("scout_tiles", "segment: scout"),
+          ("scout_quads", "segment: scout"), ("row_sum_f", "segment: scout"),
+          ("row_sums_to_pd", "segment: finish_stats"))
 
 
 def func_ranges(src_lines):
