@@ -19,6 +19,7 @@ SOURCES = ["ewk_mfcc.hip", "ewk_bank.hip", "ewk_gate.hip", "ewk_level3.hip", "ew
            "ewk_tables.cpp"]
 HEADERS = ["ewk_internal.h", "ewk_engine.h", "ewk_gate.h", "ewk_rescore.h", "ewk_rs_list.h", "ewk_score.h", "ewk_db64.h", "ewk_topdb_shift.h", "ewk_chunk_plan.h",
            "ewk_snapshot.h", "ewk_snapshot_plan.h", "ewk_g711.h",
+           "ewk_gate_tree.h", "ewk_gate_detect.h", "ewk_gate_pwsum.h", "ewk_gate_rms.h", "ewk_gate_lifecycle.h",
            "ewk_mfcc_layout.h", "ewk_mfcc_dft.h", "ewk_mfcc_tile.h", "ewk_mfcc_fft.h", "ewk_mfcc_dct.h", "ewk_mfcc_stats.h",
            os.path.join("..", "..", "include", "ewk.h")]
 LIB = os.path.join(HERE, "libewk.so")

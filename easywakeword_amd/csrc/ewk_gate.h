@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/ewk.h"
+#include "ewk_gate_tree.h"
 
 namespace ewk {
 
@@ -43,31 +44,6 @@ struct LsnState {
     int32_t reentries;
 };
 constexpr int kLsnStates = EWK_LISTENERS_MAX - 1;
-
-// numpy's pairwise summation order (np.add.reduce on a contiguous float64 array,
-// numpy/_core/src/umath/loops_utils.h.src pairwise_sum) for ONE chunk of n <= 8192
-// elements, flattened on the host: leaves of <= 128 elements (8-accumulator loop),
-// and the internal nodes grouped by height so a wave evaluates each level in parallel.
-// Node ids: leaves 0..n_leaves-1, internal node k has id n_leaves + k.
-constexpr int kPwChunk = 8192;
-constexpr int kPwMaxLeaves = 256;
-constexpr int kPwMaxLevels = 16;
-struct PwTree {
-    int32_t n;
-    int32_t n_leaves;
-    int32_t n_levels;
-    int32_t balanced;   // 1: 2^d <= 16 leaves of one length >= 8, combined pairwise in leaf order (tree_sumsq's register path)
-    int16_t leaf_start[kPwMaxLeaves];
-    int16_t leaf_len[kPwMaxLeaves];
-    int16_t left[kPwMaxLeaves];     // internal node k = val[left[k]] + val[right[k]]
-    int16_t right[kPwMaxLeaves];
-    int16_t level_end[kPwMaxLevels];   // internal nodes of height h+1: [level_end[h-1], level_end[h])
-};
-// The gate's summation lengths: the callback block (frame_size) and the last 0.1 s,
-// each as a full-chunk tree (n = 8192, used when the length exceeds one chunk) and
-// the tree of the final (or only) chunk.
-enum { kTreeBlockFull = 0, kTreeBlockRem = 1, kTreeLastFull = 2, kTreeLastRem = 3, kNumTrees = 4 };
-void build_pw_tree(int n, PwTree* t);
 
 struct GateArgs {
     const float* pcm;        // stream s, tick t: pcm[s*stride + t*tick_stride + i]
@@ -121,6 +97,22 @@ struct GateArgs {
     LsnState* lsn_st;
 };
 
+// The dynamic LDS of k_gate_ticks, as byte offsets: four wave areas (one per wave: the tree node
+// values / sort scratch, then the stage at `stage`, both rounded to 16 B; `per_wave` each), the
+// two sub-chunk trees at `trees`, and with listeners the lanes' times at `lsn` (kLsnWaveLds per
+// wave).  stage_es: bytes per staged sample (2 in the DMA 3 instantiations, which stage int16).
+constexpr size_t kLsnWaveLds = 4 * EWK_LISTENERS_MAX * sizeof(double);
+struct GateLds {
+    size_t stage, per_wave, trees, lsn, total;
+    __host__ __device__ GateLds(int32_t val_len, int32_t stage_len, int stage_es, bool listeners) {
+        stage = ((size_t)val_len * 8 + 15) & ~(size_t)15;
+        per_wave = stage + (((size_t)stage_len * stage_es + 15) & ~(size_t)15);
+        trees = 4 * per_wave;
+        lsn = trees + 2 * sizeof(PwTree);
+        total = lsn + (listeners ? 4 * kLsnWaveLds : 0);
+    }
+};
+
 // grid_cap > 0: at most that many workgroups (ewk_create's EWK_GATE_GRID_MAX), below the
 // compile-time maximum; a wave then takes more than one row from 4 * grid_cap rows on.
 hipError_t launch_gate(const GateArgs& g, hipStream_t s, int grid_cap = 0);
@@ -158,12 +150,6 @@ inline GateFamily gate_family(const GateArgs& g) {
                        ((uintptr_t)g.pcm16 & 15) == 0;
     f.dma = f.rb == 0 ? 0 : dma4 ? 2 : vec16 ? 3 : dma ? 1 : 0;
     return f;
-}
-// How tree_sumsq evaluates a PwTree: 0 = one leaf of fewer than 8 elements (a plain loop), 1 = one
-// leaf (8 accumulators), 2 = balanced (DPP, no LDS), 3 = the general LDS tree.
-inline int pw_tree_kind(const PwTree& t) {
-    if (t.n_leaves <= 1) return t.n < 8 ? 0 : 1;
-    return t.balanced ? 2 : 3;
 }
 // ewk_reset_stream_list: streams ids[0..n) back to the state ewk_reset_streams gives every stream,
 // in one launch: ring row zeroed with k_ring_zero's agent-scope stores, block RMS row zeroed,
