@@ -37,6 +37,9 @@ NAN_MARGIN_B = 0.05
 EWK_PUSH_DEVICE = 1
 EWK_PCM_DEVICE = 1
 EWK_OUT_DEVICE = 4
+EWK_FEAT_BF16 = 8            # ewk_whisper_features_*: bf16 output
+WHISPER_MELS = 80            # ... their [n][80][n_frames] layout
+WHISPER_MAX_FRAMES = 3000
 EWK_RING_F32 = 0
 EWK_RING_I16 = 1
 EWK_SCORE_REQUIRE_TEMPLATE = 1
@@ -79,6 +82,7 @@ EXPORTS = [
     "ewk_push_chunks", "ewk_push_chunks_pcm16", "ewk_stream_pending", "ewk_chunk_plan",
     "ewk_snapshot_plan", "ewk_snapshot_info", "ewk_export_streams", "ewk_import_streams",
     "ewk_g711_table", "ewk_decode_g711", "ewk_push_g711", "ewk_push_streams_g711", "ewk_push_chunks_g711",
+    "ewk_whisper_features_events", "ewk_whisper_features_segments",
 ]
 
 
@@ -247,6 +251,9 @@ def load():
             "ewk_push_many_pcm16": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
             "ewk_normalize_segments": (C.c_int, [_P, _P, C.c_int64, _i64p, _i32p, C.c_int32, _P, C.c_int32]),
             "ewk_normalize_events": (C.c_int, [_P, C.POINTER(EwkEvent), C.c_int32, _P, C.c_int32]),
+            "ewk_whisper_features_events": (C.c_int, [_P, C.POINTER(EwkEvent), C.c_int32, _P, C.c_int32, C.c_int32]),
+            "ewk_whisper_features_segments": (C.c_int, [_P, _P, C.c_int64, _i64p, _i32p, C.c_int32, _P, C.c_int32,
+                                                        C.c_int32]),
             "ewk_decode_pcm16": (C.c_int, [_P, _P, C.c_int64, _P, C.c_int32]),
             "ewk_compact_positives": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int64, C.c_int64, _P, _P, C.c_int32, _P]),
             "ewk_bank_set": (C.c_int, [_P, C.c_int32, _i32p, _fp, _fp, _dp]),

@@ -14,8 +14,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["ewk_mfcc.hip", "ewk_bank.hip", "ewk_gate.hip", "ewk_level3.hip", "ewk_gather.hip", "ewk_resample.hip",
-           "ewk_chunks.hip", "ewk_snapshot.hip", "ewk_engine.cpp", "ewk_engine_score.cpp", "ewk_engine_stream.cpp", "ewk_engine_chunks.cpp",
-           "ewk_engine_assign.cpp", "ewk_engine_poll.cpp", "ewk_engine_resample.cpp", "ewk_engine_snapshot.cpp",
+           "ewk_chunks.hip", "ewk_snapshot.hip", "ewk_whisper.hip", "ewk_engine.cpp", "ewk_engine_score.cpp", "ewk_engine_stream.cpp", "ewk_engine_chunks.cpp",
+           "ewk_engine_assign.cpp", "ewk_engine_poll.cpp", "ewk_engine_resample.cpp", "ewk_engine_snapshot.cpp", "ewk_engine_whisper.cpp",
            "ewk_tables.cpp"]
 HEADERS = ["ewk_internal.h", "ewk_engine.h", "ewk_gate.h", "ewk_rescore.h", "ewk_rs_list.h", "ewk_score.h", "ewk_db64.h", "ewk_topdb_shift.h", "ewk_chunk_plan.h",
            "ewk_snapshot.h", "ewk_snapshot_plan.h", "ewk_g711.h",

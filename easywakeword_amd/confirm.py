@@ -111,6 +111,25 @@ class WhisperConfirm:
             return list(self.processor.batch_decode(tokens, skip_special_tokens=True))
         return ["" for _ in range(len(batch))]
 
+    def features_from_events(self, engine, events):
+        """The model's input for polled events, straight from `engine`'s rings by the HIP front end
+        (StreamEngine.whisper_features_events): [n, 80, 3000] bfloat16 on the engine's device --
+        log_mel(engine.normalize_events_device(events)) without the 30 s buffers and the STFT."""
+        return engine.whisper_features_events(events, n_frames=N_FRAMES, dtype="bfloat16")
+
+    def transcribe_events(self, engine, events) -> List[str]:
+        """transcribe() of polled events, fed from features_from_events."""
+        if not len(events):
+            return []
+        torch = self.torch
+        with torch.no_grad():
+            feats = self.features_from_events(engine, events).to(device=self.device, dtype=self.dtype)
+            tokens = self.model.generate(input_features=feats, max_new_tokens=self.max_new_tokens,
+                                         do_sample=False)
+        if self.processor is not None:
+            return list(self.processor.batch_decode(tokens, skip_special_tokens=True))
+        return ["" for _ in range(len(events))]
+
     def __call__(self, audio: np.ndarray) -> Optional[str]:
         """The WakeWord ``confirm`` callable: one normalised segment -> text."""
         return self.transcribe([audio])[0] or None

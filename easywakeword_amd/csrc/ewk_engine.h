@@ -296,6 +296,20 @@ struct ewk_engine {
     // list reset with a rate set: set where a stream's history was cleared, cleared by its next push
     ewk::DevBuf<uint8_t> rs_flags;
 
+    // Level-3 front end (ewk_whisper_features_*, ewk_engine_whisper.cpp); nothing is allocated
+    // before the first call.  wf_y: the segments normalised by k_normalize (float64, packed);
+    // wf_raw / wf_fmax: raw log-mel and maximum of every live frame; wf_seg: the per-segment plan;
+    // wf_i64 / wf_len / wf_ev: k_normalize's offsets, lengths and events; wf_pcm / wf_out: a host
+    // batch on its way in and host-bound features on their way out.  All grow behind the stream.
+    ewk::DevBuf<ewk::WhisperTables> wf_tab;
+    ewk::DevBuf<double> wf_y;
+    ewk::DevBuf<float> wf_raw, wf_fmax, wf_pcm;
+    ewk::DevBuf<ewk::WfSeg> wf_seg;
+    ewk::DevBuf<int64_t> wf_i64;
+    ewk::DevBuf<int32_t> wf_len;
+    ewk::DevBuf<ewk_event> wf_ev;
+    ewk::DevBuf<unsigned char> wf_out;
+
     // measurement: (start, stop) event pairs per kernel family
     bool prof = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[6];
@@ -364,6 +378,9 @@ BankArgs bank_args(ewk_engine* e);
 int bank_follow_threshold(ewk_engine* e, hipStream_t s);
 enum WordOf { kOfSegment, kOfStream };   // "word index W of {segment|stream} I is outside [0, N)"
 int fail_word_index(int32_t word, WordOf of, int32_t i, int32_t n_words);
+// polled events about to be read from the rings: EWK_EINVAL for one outside them or from a tick not
+// pushed, EWK_EOVERWRITTEN for one whose samples its stream has overwritten since
+int check_ring_events(ewk_engine* e, const ewk_event* events, int32_t n);
 // ewk_engine_resample.cpp: a push's resample stage -- every tick at *src into rs_out (float32 16 kHz
 // blocks, where *src then points), the history saved for the next push; d_list: ResampleArgs::ids
 int resample_ticks(ewk_engine* e, TickSrc* src, int32_t rows, int32_t n_ticks, const int32_t* d_list, hipStream_t s);

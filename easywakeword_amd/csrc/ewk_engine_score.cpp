@@ -533,11 +533,7 @@ int ewk_normalize_segments(ewk_engine* e, const float* pcm, int64_t n_pcm, const
     return normalize_impl(e, d_pcm, offsets, lengths, nullptr, n_seg, out, flags);
 }
 
-int ewk_normalize_events(ewk_engine* e, const ewk_event* events, int32_t n, double* out, int32_t flags) {
-    if (!e) return fail(EWK_EINVAL, "engine is NULL");
-    if (n < 0) return fail(EWK_EINVAL, "negative size");
-    if (n == 0) return EWK_OK;
-    if (!events || !out) return fail(EWK_EINVAL, "NULL argument");
+int ewk::check_ring_events(ewk_engine* e, const ewk_event* events, int32_t n) {
     if (e->n_streams <= 0) return fail(EWK_EINVAL, "engine has no streams");
     for (int32_t i = 0; i < n; ++i) {
         const ewk_event& ev = events[i];
@@ -560,6 +556,16 @@ int ewk_normalize_events(ewk_engine* e, const ewk_event* events, int32_t n, doub
                                         "): the ring has overwritten its samples since (now tick " +
                                         std::to_string(now) + "); read positives right after their poll");
     }
+    return EWK_OK;
+}
+
+int ewk_normalize_events(ewk_engine* e, const ewk_event* events, int32_t n, double* out, int32_t flags) {
+    if (!e) return fail(EWK_EINVAL, "engine is NULL");
+    if (n < 0) return fail(EWK_EINVAL, "negative size");
+    if (n == 0) return EWK_OK;
+    if (!events || !out) return fail(EWK_EINVAL, "NULL argument");
+    int rc = check_ring_events(e, events, n);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(e->device));
     return normalize_impl(e, nullptr, nullptr, nullptr, events, n, out, flags);
 }

@@ -343,4 +343,50 @@ hipError_t launch_compact_positives(const double* score, const uint8_t* match, i
                                     int64_t step, ewk_positive* out, int32_t* d_count, int32_t* scratch, int append,
                                     hipStream_t s);
 
+// Level-3 front end (ewk_whisper.hip): Whisper's log-mel features (include/ewk.h,
+// ewk_whisper_features_*) of segments k_normalize has written as float64.  Segment i is
+// y[seg[i].y_off ..][:seg[i].len], len already cut to n_frames * 160.  Frame t of it reads samples
+// 160 t - 200 .. 160 t + 199 (reflected at 0 and at n_frames * 160), so the first
+// n_live = min(n_frames, (len + 199) / 160 + 1) frames (0 for len = 0) read a sample of the segment
+// and every later one reads only pad zeros.  k_whisper_frames writes the raw log-mel of the live
+// frames to raw[(seg[i].raw_off + t) * 80 + m] and the frame's maximum over m to
+// fmax[seg[i].raw_off + t] (NaN for a frame that read a NaN); k_whisper_finish reduces a
+// segment's maxima, clamps, scales and writes out[i][m][t] for every t < n_frames.
+constexpr int kWfFft = 400;
+constexpr int kWfHop = 160;
+constexpr int kWfBins = kWfFft / 2 + 1;   // 201
+constexpr int kWfMels = 80;
+constexpr int kWfMaxFrames = 3000;
+constexpr int kWfMelCap = 512;            // packed non-zero mel weights (about 2 per bin)
+constexpr int kWfFramesPerBlock = 8;      // k_whisper_frames: two frames per wave
+constexpr int kWfTile = 64;               // k_whisper_finish: frames per workgroup
+struct WhisperTables {
+    float win[kWfFft];                 // periodic Hann, 0.5 - 0.5 cos(2 pi i / 400)
+    float c25[25], s25[25];            // cos, sin (2 pi j / 25)
+    float c400[kWfFft], s400[kWfFft];  // cos, sin (2 pi j / 400)
+    // float32 of confirm._slaney_mel(16000, 400, 80), packed: band m = weights
+    // mel_w[mel_off[m] .. mel_off[m] + mel_n[m]) on bins mel_lo[m], mel_lo[m] + 1, ...
+    float mel_w[kWfMelCap];
+    int32_t mel_lo[kWfMels], mel_n[kWfMels], mel_off[kWfMels];
+    int32_t ok;                        // the packed weights fit kWfMelCap
+};
+void build_whisper_tables(WhisperTables* t);
+struct WfSeg {
+    int64_t y_off;      // first sample of the segment in WfArgs::y
+    int64_t raw_off;    // first live frame of the segment in raw / fmax (frames)
+    int32_t len;        // min(length, n_frames * 160)
+    int32_t n_live;
+};
+struct WfArgs {
+    const double* y;
+    const WfSeg* seg;
+    const WhisperTables* tab;
+    float* raw;          // [sum n_live][80]
+    float* fmax;         // [sum n_live]
+    void* out;           // [n_seg][80][n_frames] float32, or bf16 bits
+    int32_t n_seg, n_frames, bf16;
+    int32_t max_live;    // the largest n_live
+};
+hipError_t launch_whisper_features(const WfArgs& a, hipStream_t s);
+
 }  // namespace ewk

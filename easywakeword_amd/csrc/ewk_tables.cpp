@@ -247,6 +247,53 @@ void resample_taps(int32_t up, int32_t down, double* h) {
     for (int64_t k = 0; k < n; ++k) h[k] = h[k] / (double)sum * (double)up;   // unit DC gain, then * up
 }
 
+// Level-3 front end (ewk_whisper.hip): every entry computed in float64 and rounded once.  The mel
+// weights are confirm._slaney_mel(16000, 400, 80): Slaney triangles times 2 / (f[m + 2] - f[m]) in
+// float64, then float32.
+void build_whisper_tables(WhisperTables* t) {
+    memset(t, 0, sizeof(*t));
+    for (int i = 0; i < kWfFft; ++i) {
+        t->win[i] = (float)(0.5 - 0.5 * cos(2.0 * kPi * i / kWfFft));
+        t->c400[i] = (float)cos(2.0 * kPi * i / kWfFft);
+        t->s400[i] = (float)sin(2.0 * kPi * i / kWfFft);
+    }
+    for (int i = 0; i < 25; ++i) {
+        t->c25[i] = (float)cos(2.0 * kPi * i / 25.0);
+        t->s25[i] = (float)sin(2.0 * kPi * i / 25.0);
+    }
+    std::vector<double> fft = linspace(0.0, 8000.0, kWfBins);
+    std::vector<double> mels = linspace(hz_to_mel(0.0), hz_to_mel(8000.0), kWfMels + 2);
+    std::vector<double> mel_f(kWfMels + 2);
+    for (int i = 0; i < kWfMels + 2; ++i) mel_f[i] = mel_to_hz(mels[i]);
+    int used = 0;
+    t->ok = 1;
+    for (int m = 0; m < kWfMels; ++m) {
+        const double fd0 = mel_f[m + 1] - mel_f[m], fd1 = mel_f[m + 2] - mel_f[m + 1];
+        const double enorm = 2.0 / (mel_f[m + 2] - mel_f[m]);
+        float w[kWfBins];
+        int lo = -1, hi = -1;
+        for (int k = 0; k < kWfBins; ++k) {
+            const double lower = -(mel_f[m] - fft[k]) / fd0, upper = (mel_f[m + 2] - fft[k]) / fd1;
+            const double tri = std::max(0.0, std::min(lower, upper));
+            w[k] = (float)(tri * enorm);
+            if (w[k] != 0.0f) {
+                if (lo < 0) lo = k;
+                hi = k;
+            }
+        }
+        const int n = lo < 0 ? 0 : hi - lo + 1;
+        if (used + n > kWfMelCap) {
+            t->ok = 0;
+            return;
+        }
+        t->mel_lo[m] = lo < 0 ? 0 : lo;
+        t->mel_n[m] = n;
+        t->mel_off[m] = used;
+        for (int q = 0; q < n; ++q) t->mel_w[used + q] = w[lo + q];
+        used += n;
+    }
+}
+
 void table_window(double* w) { hann_periodic(w); }
 void table_mel(float* w) { mel_dense(w); }
 void table_dct(double* d) { dct_rows(d); }

@@ -328,6 +328,41 @@ class Engine:
                                                out.ctypes.data_as(C.c_void_p), 0))
         return [out[o:o + l] for o, l in zip(offsets, lengths)]
 
+    def _feature_out(self, n: int, n_frames: int, dtype: str):
+        """The [n, 80, n_frames] output tensor of a whisper_features* call and its flags."""
+        import torch
+        if dtype not in ("float32", "bfloat16"):
+            raise ValueError(f'dtype must be "float32" or "bfloat16", got {dtype!r}')
+        if not 1 <= int(n_frames) <= _lib.WHISPER_MAX_FRAMES:
+            raise ValueError(f"n_frames = {n_frames} is outside 1..{_lib.WHISPER_MAX_FRAMES}")
+        out = torch.empty((n, _lib.WHISPER_MELS, int(n_frames)), device=torch.device("cuda", self.gpu),
+                          dtype=torch.bfloat16 if dtype == "bfloat16" else torch.float32)
+        return out, _lib.EWK_OUT_DEVICE | (_lib.EWK_FEAT_BF16 if dtype == "bfloat16" else 0)
+
+    def whisper_features(self, segments, n_frames: int = 3000, dtype: str = "float32"):
+        """Whisper's log-mel input features of each segment (level-3 normalisation included;
+        include/ewk.h, ewk_whisper_features_segments): a [n, 80, n_frames] torch tensor, float32
+        or bfloat16, on this engine's device.  `segments`: float32 arrays, or (pcm, offsets,
+        lengths) with pcm a float32 torch tensor on this engine's device."""
+        pcm_dev = isinstance(segments, tuple) and len(segments) == 3 and hasattr(segments[0], "data_ptr")
+        if pcm_dev:
+            pcm_t, offsets, lengths = segments
+            if str(pcm_t.dtype) != "torch.float32" or not pcm_t.is_contiguous() or pcm_t.device.index != self.gpu:
+                raise ValueError("pcm must be a contiguous float32 tensor on this engine's device")
+            offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+            lengths = np.ascontiguousarray(lengths, dtype=np.int32)
+            pcm_ptr, n_pcm, flags_in = C.c_void_p(pcm_t.data_ptr()), pcm_t.numel(), _lib.EWK_PCM_DEVICE
+        else:
+            pcm, offsets, lengths = _pack([_f32(s) for s in segments])
+            pcm_ptr, n_pcm, flags_in = pcm.ctypes.data_as(C.c_void_p), len(pcm), 0
+        n = len(lengths)
+        out, flags = self._feature_out(n, n_frames, dtype)
+        if n:
+            check(self._lib.ewk_whisper_features_segments(self._h, pcm_ptr, n_pcm, _lib.i64ptr(offsets),
+                                                          _lib.i32ptr(lengths), n, C.c_void_p(out.data_ptr()),
+                                                          int(n_frames), flags | flags_in))
+        return out
+
     def decode_pcm16(self, pcm16: np.ndarray) -> np.ndarray:
         """int16 PCM -> float32 (x / 32768, librosa.load's value for 16 kHz PCM16) on the GPU."""
         a = np.ascontiguousarray(pcm16, dtype=np.int16)
@@ -484,6 +519,17 @@ class StreamEngine(Engine):
                                              C.c_void_p(out.data_ptr()), _lib.EWK_OUT_DEVICE))
         offs = np.concatenate([[0], np.cumsum(lengths)[:-1]])
         return [out[int(o):int(o) + int(l)] for o, l in zip(offs, lengths)]
+
+    def whisper_features_events(self, events: np.ndarray, n_frames: int = 3000, dtype: str = "float32"):
+        """Whisper's log-mel input features of polled events, read straight from the rings
+        (include/ewk.h, ewk_whisper_features_events): a [n, 80, n_frames] torch tensor, float32 or
+        bfloat16, on this engine's device.  RingOverwrittenError as for normalize_events."""
+        ev = np.ascontiguousarray(events, dtype=_lib.EVENT_DTYPE)
+        out, flags = self._feature_out(len(ev), n_frames, dtype)
+        if len(ev):
+            check(self._lib.ewk_whisper_features_events(self._h, ev.ctypes.data_as(C.POINTER(_lib.EwkEvent)), len(ev),
+                                                        C.c_void_p(out.data_ptr()), int(n_frames), flags))
+        return out
 
     def push_device(self, ptr: int, stride: int, tick_stride: int = 0, n_ticks: int = 1) -> None:
         """Device-resident float32 ticks: stream s, tick t at ptr + 4 * (s * stride + t * tick_stride);

@@ -531,6 +531,38 @@ int ewk_normalize_segments(ewk_engine* e, const float* pcm, int64_t n_pcm, const
 /* ... or gated segments straight from the stream rings (polled events: stream,
  * ring_start, length), the reference's word_audio of each event. */
 int ewk_normalize_events(ewk_engine* e, const ewk_event* events, int32_t n, double* out, int32_t flags);
+/* Level-3 front end: the input features of the Whisper model the reference hands each normalised
+ * segment to (transcriber.py:122-134), computed on the device in one call.  For a segment and
+ * n_frames frames (1..3000; 3000 is the model's 30 s window):
+ *   y   the normalisation above (float64), rounded once to float32;
+ *   x   n_frames * 160 float32 samples: y cut to that length, zeros behind it;
+ *   xp  x reflect-padded by 200 samples at both ends (xp[-j] = x[j], and x[2 n - 2 - j] past the end);
+ *   frame t = xp[160 t .. 160 t + 400) times the periodic Hann window 0.5 - 0.5 cos(2 pi i / 400);
+ *   P   the squared magnitude of its 201 rfft bins;
+ *   L   log10(max(mel @ P, 1e-10)), mel the float32 Slaney filterbank (16 kHz, n_fft 400, 80 bands);
+ *   out = (max(L, max of L over the whole [80][n_frames]) - 8) + 4) / 4.
+ * So a frame that reads only pad zeros is (max(-10, Lmax - 8) + 4) / 4, a segment that is all zeros
+ * after normalisation (or has length 0) is -1.5 everywhere, and a segment with a non-finite sample
+ * is NaN in every element.  Only the frames that read a sample of the segment are transformed.
+ * Layout: out[i][m][t], i < n, band m < 80, frame t < n_frames contiguous -- n * 80 * n_frames
+ * float32, or with EWK_FEAT_BF16 as many bf16 values, each the float32 value rounded to nearest
+ * even.  out is host memory unless flags has EWK_OUT_DEVICE.  The work runs on the engine's stream
+ * (ewk_stream_handle), behind every push and scoring pass enqueued before it, and the call returns
+ * once the features are written.  Normalised samples, raw log-mel frames and staging live in engine
+ * scratch that grows with the largest call and is shared by both entry points, so calls on one
+ * engine must not overlap.  Errors: EWK_EINVAL for n_frames outside 1..3000, unknown flags and NULL
+ * pointers; a refused call writes nothing.
+ * ... of gated segments straight from the stream rings (float32, int16 and compact rings, segments
+ * across a ring's end included): polled events as for ewk_normalize_events, refused with
+ * EWK_EOVERWRITTEN on the same rule. */
+#define EWK_FEAT_BF16 8       /* ewk_whisper_features_*: write bf16 instead of float32 */
+int ewk_whisper_features_events(ewk_engine* e, const ewk_event* events, int32_t n, void* out, int32_t n_frames,
+                                int32_t flags);
+/* ... or of segments of a linear float32 batch, shaped like ewk_normalize_segments (pcm host
+ * memory unless EWK_PCM_DEVICE; offsets and lengths are host arrays either way). */
+int ewk_whisper_features_segments(ewk_engine* e, const float* pcm, int64_t n_pcm, const int64_t* offsets,
+                                  const int32_t* lengths, int32_t n_seg, void* out, int32_t n_frames,
+                                  int32_t flags);
 /* Positives for the level-3 confirm gather (SURVEY.md 8b `ewk_gather_detections`, 8e):
  * the reference confirms every detection (wakeword.py:1120-1130); on N GPUs only the
  * positives cross xGMI.  Compacts the matched segments of a scored batch -- d_score /
