@@ -14,7 +14,8 @@
 // so the group's loads are contiguous) and reloads only when its group's word changes from one
 // step to the next.  The segment's 40 statistics and its own self-dots are the same in every
 // lane of its group.  The arithmetic is the reference's (ewk_score.h): sequential 20-term dots,
-// no contraction, pow(percent, 1.5) / 10.
+// no contraction, pow(percent, 1.5) / 10 -- for float32 candidates pow15f(percent) / 10, the
+// correctly rounded p * sqrt(p) and on purpose not powf (ewk_score.h says why).
 //
 // The stream bank (k_bank_events) is the same pass over the pending events of a streaming
 // tick: bank_pass is the one body, a source policy says where its items come from and where

@@ -112,7 +112,7 @@ __device__ __forceinline__ double score_f32_finish(float uu_m, float uu_s, float
     const float ds = clip02f(1.0f - uv_s / (float)sqrt((double)(uu_s * vv_s)));
     const float combined = (1.0f - dm) * 0.7f + (1.0f - ds) * 0.3f;
     const float percent = combined * 100.0f;
-    return (double)(powf(percent, 1.5f) / 10.0f);
+    return (double)(pow15f(percent) / 10.0f);
 }
 
 #include "ewk_rescore.h"

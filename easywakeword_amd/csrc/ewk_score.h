@@ -22,6 +22,11 @@ constexpr double kTinyStd = 20.0;   // |std vector| below which the fp64 path de
 //     float32 dot, uv / vv float64, the rest float64;
 //   float32 (WordMatcher on float32 audio): every dot float32 and, under NumPy 2
 //     scalar promotion, every following operation float32.
+// One operation is not the reference's own: its float32 percent ** 1.5 is libm's powf, which
+// no device reproduces bit for bit and which is itself misrounded now and then; the float32
+// finishes take pow15f below, the correctly rounded value.  Do not put powf back:
+// tests/test_gpu_bank_matrix.py holds the float32 scores to tests/bank_matrix.py's restatement
+// of pow15f at less than one float32 ulp.
 __device__ __forceinline__ float sdot20(const float* a, const float* b) {
 #pragma clang fp contract(off)
     double acc = 0.0;
@@ -57,6 +62,18 @@ __device__ __forceinline__ float clip02f(float d) {
     return d;
 }
 
+// percent ** 1.5 of a float32 percent (float32 candidates): p * sqrt(p) in double, rounded to
+// float32 -- two correctly rounded IEEE operations, so the value is the correctly rounded power
+// (a double rounding aside) on any device and host, where powf is whatever each math library
+// makes of it: the device's was one float32 ulp off libm's for a fifth of the scores, this is
+// for 0.07 % of percents in (0, 100] (libm's own misroundings; DESIGN.md, template bank matrix).
+// NaN for p < 0, as powf.
+__device__ __forceinline__ float pow15f(float p) {
+#pragma clang fp contract(off)
+    const double d = (double)p;
+    return (float)(d * sqrt(d));
+}
+
 // Candidate stats in float64 (the streaming dtype).
 __device__ double score_f64cand(const float* tm, const float* ts, const double* cm, const double* cs) {
 #pragma clang fp contract(off)
@@ -83,7 +100,7 @@ __device__ double score_f32cand(const float* tm, const float* ts, const float* c
     }
     const float combined = sim[0] * 0.7f + sim[1] * 0.3f;
     const float percent = combined * 100.0f;
-    return (double)(powf(percent, 1.5f) / 10.0f);
+    return (double)(pow15f(percent) / 10.0f);
 }
 
 // The same two scores from dot products the caller already holds (the template bank: the
@@ -106,7 +123,7 @@ __device__ __forceinline__ double score_f32cand_dots(float uu_m, float uu_s, flo
     const float ds = clip02f(1.0f - uv_s / (float)sqrt((double)(uu_s * vv_s)));
     const float combined = (1.0f - dm) * 0.7f + (1.0f - ds) * 0.3f;
     const float percent = combined * 100.0f;
-    return (double)(powf(percent, 1.5f) / 10.0f);
+    return (double)(pow15f(percent) / 10.0f);
 }
 
 }  // namespace ewk

@@ -10,7 +10,11 @@ HIP events after warm-up, one process, the cases alternated round by round):
 and the fraction of segments each bank case lists for the fp64 pass (a has no such read-out; with
 one template the rule of b is a's).  Prints one JSON line.
 
-    python scripts/bench_bank.py [--segments 65536] [--rounds 7] [--warmup 2] [--rescore-margin M] [--out FILE]
+    python scripts/bench_bank.py [--segments 65536] [--rounds 7] [--warmup 2] [--rescore-margin M]
+                                 [--f32-candidates] [--out FILE]
+
+--f32-candidates scores every case with float32 candidates (EWK_SCORE_F32_CANDIDATES: the float32
+finishes of ewk_score.h / ewk_mfcc.hip); the default is the streaming arithmetic, float64 candidates.
 """
 import argparse
 import json
@@ -32,6 +36,7 @@ def main():
     ap.add_argument("--rescore-margin", type=float, default=None,
                     help="rescore_margin of the bank engines (0: no near-threshold listing, which shows "
                          "what the fp64 pass costs)")
+    ap.add_argument("--f32-candidates", action="store_true")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
 
@@ -79,10 +84,11 @@ def main():
         e = engines[key]
         if key == "a":
             e.score_device(pcm.data_ptr(), d_off.data_ptr(), d_len.data_ptr(), n, mean.data_ptr(), std.data_ptr(),
-                           score.data_ptr(), match.data_ptr(), sh)
+                           score.data_ptr(), match.data_ptr(), sh, f32_candidates=args.f32_candidates)
         else:
             e.score_bank_device(pcm.data_ptr(), d_off.data_ptr(), d_len.data_ptr(), n,
-                                d_word.data_ptr() if key == "d" else 0, out.data_ptr(), 0, 0, sh)
+                                d_word.data_ptr() if key == "d" else 0, out.data_ptr(), 0, 0, sh,
+                                f32_candidates=args.f32_candidates)
 
     keys = ["a", "b", "c", "d"]
     for _ in range(args.warmup):
@@ -105,6 +111,7 @@ def main():
         torch.cuda.synchronize()
         listed[k] = float(out.cpu().numpy().view(_lib.BANK_RESULT_DTYPE)["rescored"].mean())
     res = {"segments": n, "frames": frames, "rounds": args.rounds, "rescore_margin": args.rescore_margin,
+           "f32_candidates": bool(args.f32_candidates),
            "ms_median": {k: float(np.median(v_)) for k, v_ in ms.items()},
            "ms_min": {k: float(np.min(v_)) for k, v_ in ms.items()},
            "ms_all": {k: [round(x, 4) for x in v_] for k, v_ in ms.items()},
